@@ -9,8 +9,14 @@ A "step" = one full optimisation step of the hot path on one batch of synthetic 
 backbone + FPN + RPN (losses, proposals, NMS) + RoI heads (bbox, mask, FOA offset) forward, all losses,
 backward, gradient all-reduce (RCCL over xGMI, bucketed, overlapped), clip, SGD.  Inputs are resident in HBM
 before the timed region.  Weak scaling: the per-GPU batch is fixed (8), the global batch grows with N.
-Rank 0 prints ONE JSON line (see the prompt contract) with `roofline` (dominant kernel, measured live with
-HIP events) and `cpu_baseline` (the CPU oracle -- the restated reference -- timed on the host cores).
+Rank 0 prints ONE JSON line: `metric`, `value` (img/s), `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the workload.
+
+A plain run does only that: set-up, W warm-up steps, K timed steps, the result line.  `--full` adds everything else the
+benchmark measures, each in runs of its own after the timed steps: `roofline` (dominant kernel, measured live with HIP events),
+`value_random_init_rpn` (second timed loop), `value_fp32_parity` / `value_mixed` (the fp32-grade modes), `comm_forced_1rank`
+(child runs with the gradient reducer forced on), `cpu_baseline` (the CPU oracle -- the restated reference -- timed on the host
+cores) and `offset_epe_vs_ref`.  `--dump-outputs DIR` replays the last timed step from the seeded start and writes what it
+computed as DIR/<name>.npy (see dump_outputs) so that two builds can be compared output for output on identical inputs.
 """
 import argparse
 import json
@@ -50,7 +56,13 @@ def parse():
     ap.add_argument('--stream-form', type=int, default=-1, help='A/B: the form of the two-stage 256 x 256 stream schedule the dispatcher launches '
                     '(include/loft_hip.h loft_conv_stream_form: 0 round 2, 1 activations first, 2 lean, 3 both; -1 = the library default)')
     ap.add_argument('--cpu-threads', type=int, default=0, help='threads of the cpu_baseline leg (0: min(host cores, 32))')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true', help='after the timed steps, also run every other leg (roofline, random-init RPN '
+                    'load, fp32-grade modes, forced reducer, CPU baseline, offset EPE vs the reference); the --no-* switches still apply')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed to DIR/<name>.npy')
+    args = ap.parse_args()
+    if not args.full:           # a plain run: only what the headline figure needs
+        args.no_light = args.no_roofline = args.no_fp32 = args.no_forced_comm = args.no_cpu_baseline = True
+    return args
 
 
 def f_train_gflop(n_roi, n_pos, sparse_rpn_backward=True):
@@ -182,6 +194,41 @@ def offset_epe_vs_ref():
     return out
 
 
+def train_state(trainer):
+    """Everything a training step reads besides its batch: weights, momenta, model buffers, iteration, sampler draw count and the
+    RNG states (copies)."""
+    from bonai_amd import kernels as K
+    return dict(data=trainer.arena.data.clone(), momentum=trainer.arena.momentum.clone(),
+                buffers=[b.clone() for b in trainer.model.buffers()], iter=trainer.iter, sampler_calls=K._SAMPLE_CALLS[0],
+                rng=torch.get_rng_state(), cuda_rng=torch.cuda.get_rng_state())
+
+
+def set_train_state(trainer, st):
+    """Inverse of train_state, in place (captured graphs and views keep their addresses)."""
+    from bonai_amd import kernels as K
+    trainer.arena.data.copy_(st['data'])
+    trainer.arena.momentum.copy_(st['momentum'])
+    for b, v in zip(trainer.model.buffers(), st['buffers']):
+        b.copy_(v)
+    trainer.iter, K._SAMPLE_CALLS[0] = st['iter'], st['sampler_calls']
+    torch.set_rng_state(st['rng'])
+    torch.cuda.set_rng_state(st['cuda_rng'])
+
+
+def dump_outputs(d, out, trainer, n=1 << 22):
+    """What the (replayed) last timed step handed its caller, as DIR/<name>.npy: every loss of its log_vars (float64, one file per key) and
+    the same seeded sample of n entries of the flat parameter arena after the SGD update (params_sample) and of the gradient the
+    step computed (grads_sample), float32 -- 2 x 16 MiB at the default n."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for k, v in out['log_vars'].items():
+        np.save(os.path.join(d, f'{k}.npy'), np.asarray([v], np.float64))
+    a = trainer.arena
+    idx = torch.randint(0, a.numel, (min(n, a.numel),), generator=torch.Generator().manual_seed(0)).sort()[0].to(a.data.device)
+    np.save(os.path.join(d, 'params_sample.npy'), a.data.index_select(0, idx).cpu().numpy())
+    np.save(os.path.join(d, 'grads_sample.npy'), a.grad.index_select(0, idx).cpu().numpy())
+
+
 def forced_comm_leg(args, plain_ms):
     """N = 1: the same timed loop in a CHILD process with the gradient reducer forced on over a one-rank RCCL group
     (`bench.py --force-reducer`): 25 MiB buckets released by the gradient hooks, one ncclAllReduce per bucket on the side
@@ -283,6 +330,7 @@ def main():
                       graph_features=args.graph)
     data = make_batch(args.batch, args.size, args.num_gt, rank=rank, device='cuda')
     n_pos, n_roi = [], []
+    start = train_state(trainer) if args.dump_outputs else None
     comm = None
     if world > 1 or force:
         seen = torch.ones(1, device='cuda')
@@ -293,9 +341,10 @@ def main():
                     grad_mib_per_step=round(trainer.arena.numel * 4 / 2 ** 20, 1))
 
     def one_step(it):
-        trainer.train_step(data, lr=step_lr(cfg.optimizer.lr, it, 0))
+        out = trainer.train_step(data, lr=step_lr(cfg.optimizer.lr, it, 0))
         n_pos.append(model.roi_head.last_stats['num_pos'])
         n_roi.append(model.roi_head.last_stats['num_rois'])
+        return out
 
     rank_pos = []
 
@@ -372,6 +421,20 @@ def main():
         ex = trainer.reducer.exposed_ms()
         comm['exposed_ms'] = None if ex is None else round(ex, 3)
         trainer.reducer.measure = False
+    if start is not None:
+        # The timed steps train, and their gradient sums are fp32 / packed-bf16 atomics whose order varies from run to run: after
+        # W + K updates the weights (and through proposal ranking and sampling, the losses) differ between runs by far more than
+        # rounding.  So the last timed step is replayed -- its batch, iteration, learning rate and sampler draws -- from the seeded
+        # state the warm-up started from; only that one step's own summation order then differs between runs.  The trained state
+        # is put back afterwards for whatever runs next.
+        last_it = args.warmup + args.steps - 1
+        cps = (K._SAMPLE_CALLS[0] - start['sampler_calls']) // (last_it + 1)      # sampler draws per step
+        trained = train_state(trainer)
+        set_train_state(trainer, dict(start, iter=start['iter'] + last_it, sampler_calls=start['sampler_calls'] + cps * last_it))
+        out = one_step(last_it)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, out, trainer)
+        set_train_state(trainer, trained)
     elapsed = ms_step * args.steps / 1e3
     if saturate and not args.no_light:
         model.rpn_head.forward_train = orig_ft

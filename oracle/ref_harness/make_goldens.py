@@ -4,6 +4,7 @@ outputs, a few hundred KB) are committed, the reference is not.
 
     python oracle/ref_harness/make_goldens.py
 """
+import json
 import os
 import sys
 
@@ -443,6 +444,23 @@ def data_pipeline():
     print('data_pipeline.npz', out['roof_bboxes'].shape, out['building_polar_offsets'][:2], float(out['roof_angle']))
 
 
+def model_surface():
+    """The state_dict surface of the reference's LOFT model, built by the reference's own ``build_detector`` from its own config:
+    every key with its shape, and the named parameters in registration order with requires_grad (what tests/test_plugin_cpu.py
+    holds the plugin-built model to)."""
+    from mmdet.models import build_detector
+    from bonai_amd.config import Config
+    cfg = Config.fromfile(os.path.join(mmcv_stub.REFERENCE_ROOT, 'configs', 'loft_foa', 'loft_foa_r50_fpn_2x_bonai.py'))
+    cfg.model['pretrained'] = None
+    m = build_detector(cfg.model, train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg)
+    out = dict(state_dict=[[k, list(v.shape)] for k, v in m.state_dict().items()],
+               parameters=[[n, list(p.shape), p.requires_grad] for n, p in m.named_parameters()])
+    with open(os.path.join(GOLD, 'reference_model_surface.json'), 'w') as f:       # one entry per line: readable diffs
+        f.write('{\n' + ',\n'.join(f'{json.dumps(k)}: [\n' + ',\n'.join(json.dumps(e) for e in v) + '\n]' for k, v in out.items())
+                + '\n}\n')
+    print('reference_model_surface.json', len(out['state_dict']), 'keys', len(out['parameters']), 'parameters')
+
+
 if __name__ == '__main__':
     torch.manual_seed(0)
     if len(sys.argv) > 1 and sys.argv[1] == 'data':
@@ -462,6 +480,9 @@ if __name__ == '__main__':
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == 'foa_variants':
         foa_variants()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == 'model_surface':
+        model_surface()
         sys.exit(0)
     core_ops()
     e2e()

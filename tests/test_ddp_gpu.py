@@ -285,7 +285,7 @@ def test_bench_launch_contract_two_ranks():
     env = dict(os.environ, LOFT_BENCH_SHARED_GPU='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
-           '--batch', '2', '--size', '512', '--num-gt', '20']
+           '--batch', '2', '--size', '512', '--num-gt', '20', '--full']
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]

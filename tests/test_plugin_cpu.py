@@ -1,31 +1,72 @@
-"""CPU, build container only: the reference-side plugin (bonai_amd/mmdet_plugin.py) EXECUTED against the
-reference tree -- the reference's own ``mmdet.models.build_detector`` (mmdet/models/builder.py:65-67) on the reference's own
-config file must come back built from bonai_amd classes, with the state_dict surface of the reference's model.
+"""CPU: the reference-side plugin (bonai_amd/mmdet_plugin.py) EXECUTED against the registries of the
+reference's builders -- ``build_detector`` (mmdet/models/builder.py:65-67) on the LOFT config must come back built from bonai_amd
+classes, with the state_dict surface of the reference's model.
 
-Needs /root/reference (absent on the GPU box: skipped there) and the stand-in mmcv of oracle/ref_harness/mmcv_stub.py."""
+The reference's builder modules are a Registry per type family plus ``build_from_cfg`` (mmcv 1.0.5, restated in
+oracle/ref_harness/mmcv_stub.py); they are stood in for here, each registry pre-filled with a foreign placeholder under every name
+the plugin must replace.  The reference model's surface (keys, shapes, parameter registration order) is the fixture
+tests/golden/reference_model_surface.json, made by the reference's own build_detector (oracle/ref_harness/make_goldens.py
+model_surface)."""
+import json
 import os
 import sys
+import types
 import warnings
 
 import pytest
 
-REF = '/root/reference'
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'mmdet')), reason='reference tree not present on this box')
+
+_BUILDERS = {'mmdet.models.builder': ('DETECTORS', 'BACKBONES', 'NECKS', 'HEADS', 'ROI_EXTRACTORS', 'SHARED_HEADS', 'LOSSES'),
+             'mmdet.core.bbox.builder': ('BBOX_ASSIGNERS', 'BBOX_SAMPLERS', 'BBOX_CODERS'),
+             'mmdet.core.anchor.builder': ('ANCHOR_GENERATORS',),
+             'mmdet.core.bbox.iou_calculators.builder': ('IOU_CALCULATORS',)}
 
 
-def test_reference_build_detector_resolves_to_native_classes():
+def _stand_in_mmdet(monkeypatch):
+    """sys.modules entries for the reference's builder modules: one mmcv-style Registry per family, holding a placeholder class
+    (module 'mmdet.stock') under every name bonai_amd.loft registers, and the reference's build functions over them."""
     sys.path.insert(0, os.path.join(ROOT, 'oracle', 'ref_harness'))
-    import mmcv_stub
-    mmcv_stub.install()
-    from mmdet.models import build_detector          # the REFERENCE's builder
+    from mmcv_stub import Registry, build_from_cfg
+    import bonai_amd.loft as L
+    mods = {}
+    for full in ['mmdet', 'mmdet.models', 'mmdet.core', 'mmdet.core.bbox', 'mmdet.core.anchor', 'mmdet.core.bbox.iou_calculators',
+                 *_BUILDERS]:
+        mods[full] = types.ModuleType(full)
+        mods[full].__path__ = []
+        monkeypatch.setitem(sys.modules, full, mods[full])
+    for modname, regs in _BUILDERS.items():
+        for reg in regs:
+            r = Registry(reg.lower())
+            for name in getattr(L, reg).module_dict:
+                r.register_module(name=name, module=type(name, (), {'__module__': 'mmdet.stock'}))
+            setattr(mods[modname], reg, r)
+    mb, bb = mods['mmdet.models.builder'], mods['mmdet.core.bbox.builder']
+
+    def build(cfg, registry, default_args=None):
+        if isinstance(cfg, list):
+            import torch.nn as nn
+            return nn.Sequential(*[build_from_cfg(c, registry, default_args) for c in cfg])
+        return build_from_cfg(cfg, registry, default_args)
+    mb.build_backbone = lambda cfg: build(cfg, mb.BACKBONES)
+    mb.build_head = lambda cfg: build(cfg, mb.HEADS)
+    mb.build_detector = lambda cfg, train_cfg=None, test_cfg=None: build(cfg, mb.DETECTORS, dict(train_cfg=train_cfg, test_cfg=test_cfg))
+    bb.build_bbox_coder = lambda cfg, **default_args: build_from_cfg(cfg, bb.BBOX_CODERS, default_args)
+    mods['mmdet.models'].build_detector = mb.build_detector
+    return mb, bb
+
+
+def test_reference_build_detector_resolves_to_native_classes(monkeypatch, golden_dir):
+    mb, bb = _stand_in_mmdet(monkeypatch)
+    from mmdet.models import build_detector          # the reference's builder (stand-in registries)
     from bonai_amd.config import Config
     import bonai_amd.loft as L
-    cfg = Config.fromfile(os.path.join(REF, 'configs', 'loft_foa', 'loft_foa_r50_fpn_2x_bonai.py'))   # the REFERENCE's config
+    cfg = Config.fromfile(os.path.join(ROOT, 'configs', 'loft_foa', 'loft_foa_r50_fpn_2x_bonai.py'))
     cfg.model['pretrained'] = None
-    ref_model = build_detector(cfg.model, train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg)
-    assert type(ref_model).__module__.startswith('mmdet.')
-    ref_keys = {k: tuple(v.shape) for k, v in ref_model.state_dict().items()}
+    ref = json.load(open(os.path.join(golden_dir, 'reference_model_surface.json')))
+    ref_keys = {k: tuple(s) for k, s in ref['state_dict']}
+    with pytest.raises(TypeError):                  # before register(): the registries hold the stock (foreign) classes
+        build_detector(cfg.model, train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg)
 
     import bonai_amd.mmdet_plugin as plugin
     done = plugin.register()
@@ -33,7 +74,9 @@ def test_reference_build_detector_resolves_to_native_classes():
                  'OffsetHeadExpandFeature', 'OffsetHead', 'CrossEntropyLoss', 'L1Loss', 'SmoothL1Loss', 'MaxIoUAssigner',
                  'RandomSampler', 'DeltaXYWHBBoxCoder', 'DeltaXYOffsetCoder', 'AnchorGenerator', 'BboxOverlaps2D', 'HRNet', 'HRFPN'):
         assert any(name in v for v in done.values()), name
-    model = build_detector(cfg.model, train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg)      # same call, same config
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        model = build_detector(cfg.model, train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg)      # same call, same config
     assert type(model) is L.DETECTORS.get('LOFT')
     native = [m for m in model.modules() if type(m).__module__.startswith('bonai_amd.')]
     foreign = [type(m).__name__ for m in model.modules()
@@ -44,7 +87,7 @@ def test_reference_build_detector_resolves_to_native_classes():
     # ... and in the reference's REGISTRATION ORDER: torch.optim.SGD's state_dict indexes parameters by their position in
     # model.parameters(), so Trainer.load_optimizer_state can take a reference checkpoint's 'optimizer' entry only if the
     # i-th parameter here is the i-th parameter there (engine.py)
-    ref_order = [(n, tuple(p.shape), p.requires_grad) for n, p in ref_model.named_parameters()]
+    ref_order = [(n, tuple(s), g) for n, s, g in ref['parameters']]
     own_order = [(n, tuple(p.shape), p.requires_grad) for n, p in model.named_parameters()]
     assert own_order == ref_order
     # sub-builders of the reference resolve too

@@ -7,7 +7,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
 rm -rf /tmp/prof_f32
-LOFT_BENCH_F32_ONLY=1 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_f32 -- python "$ROOT/bench.py" --no-cpu-baseline \
+LOFT_BENCH_F32_ONLY=1 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_f32 -- python "$ROOT/bench.py" --full --no-cpu-baseline \
     --no-light --no-forced-comm --no-roofline --steps 2 --warmup 1 > "$OUT/fp32_profile_bench.json" 2> /dev/null
 f=$(find /tmp/prof_f32 -name '*kernel_stats.csv' | head -1)
 [ -n "$f" ] && cp "$f" "$OUT/fp32_kernel_stats.csv"

@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/refresh
 mkdir -p "$OUT"
 cd "$ROOT"
-LOFT_DUMP_SHAPES=1 python bench.py > "$OUT/bench_line.json" 2> "$OUT/bench.err"
+LOFT_DUMP_SHAPES=1 python bench.py --full > "$OUT/bench_line.json" 2> "$OUT/bench.err"
 grep '^#' "$OUT/bench.err" > "$OUT/bench_shapes.txt"
 python - <<'PY'
 import json

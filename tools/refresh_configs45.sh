@@ -7,9 +7,9 @@ export TMPDIR=/tmp
 cd /tmp
 for c in config4_dcn:loft_foa_r50_fpn_mdconv_c3-c5_2x_bonai.py config5_hrnet:loft_foa_hrnetv2p_w32_2x_bonai.py; do
     tag=${c%%:*}; cfg=${c##*:}
-    python "$ROOT/bench.py" --config $cfg --no-cpu-baseline > "$OUT/${tag}_bench_line.json" 2> /dev/null
+    python "$ROOT/bench.py" --full --config $cfg --no-cpu-baseline > "$OUT/${tag}_bench_line.json" 2> /dev/null
     rm -rf /tmp/prof_$tag
-    rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$tag -- python "$ROOT/bench.py" --config $cfg --no-cpu-baseline \
+    rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$tag -- python "$ROOT/bench.py" --full --config $cfg --no-cpu-baseline \
         --no-roofline --steps 10 > /dev/null 2>&1
     f=$(find /tmp/prof_$tag -name '*kernel_stats.csv' | head -1)
     [ -n "$f" ] && cp "$f" "$OUT/${tag}_kernel_stats.csv"

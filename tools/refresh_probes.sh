@@ -22,7 +22,7 @@ timeout 300 python tools/probes/bucket_timeline.py 2>&1 | grep -E "^  bucket|red
 timeout 300 python tools/probes/hipblaslt_ref.py > "$OUT/hipblaslt_ref.txt" 2>&1
 timeout 300 python tools/probes/aten_sites.py > "$OUT/aten_sites.txt" 2>&1
 ( cd /tmp; export TMPDIR=/tmp; rm -rf /tmp/fill_prof
-  timeout 400 rocprofv3 --kernel-trace --output-format csv -d /tmp/fill_prof -- python "$ROOT/bench.py" --no-cpu-baseline --no-saturate --no-roofline > /dev/null 2>&1
+  timeout 400 rocprofv3 --kernel-trace --output-format csv -d /tmp/fill_prof -- python "$ROOT/bench.py" --full --no-cpu-baseline --no-saturate --no-roofline > /dev/null 2>&1
   f=$(find /tmp/fill_prof -name '*kernel_trace.csv' | head -1)
   python "$ROOT/tools/probes/fill_profile.py" "$f" > "$OUT/fill_profile.txt" 2>&1
   python "$ROOT/tools/probes/gap_profile.py" "$f" >> "$OUT/fill_profile.txt" 2>&1 )

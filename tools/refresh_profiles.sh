@@ -16,12 +16,12 @@ W=5; K=20
 for mode in serial default; do
     rm -rf /tmp/prof_$mode
     if [ $mode = serial ]; then export LOFT_NO_SIDE_STREAM=1; else unset LOFT_NO_SIDE_STREAM; fi
-    timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$mode -- python "$ROOT/bench.py" --no-cpu-baseline --no-light \
+    timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$mode -- python "$ROOT/bench.py" --full --no-cpu-baseline --no-light \
         --no-fp32 --no-forced-comm --steps $K --warmup $W > "$OUT/bench_under_rocprof_$mode.json" 2> /dev/null
     f=$(find /tmp/prof_$mode -name '*kernel_stats.csv' | head -1)
     [ -n "$f" ] && cp "$f" "$OUT/kernel_stats_$mode.csv"
     # steps the summary covers: W warm-up + K timed + 2 instrumented (bench.py's roofline leg)
-    echo "{\"source_hash\": \"$HASH\", \"steps_profiled\": $((W + K + 2)), \"command\": \"bench.py --no-cpu-baseline --no-light --no-fp32 --no-forced-comm --steps $K --warmup $W\", \"mode\": \"$mode\"}" > "$OUT/kernel_stats_$mode.meta.json"
+    echo "{\"source_hash\": \"$HASH\", \"steps_profiled\": $((W + K + 2)), \"command\": \"bench.py --full --no-cpu-baseline --no-light --no-fp32 --no-forced-comm --steps $K --warmup $W\", \"mode\": \"$mode\"}" > "$OUT/kernel_stats_$mode.meta.json"
 done
 unset LOFT_NO_SIDE_STREAM
 cp "$OUT/kernel_stats_serial.csv" "$ROOT/profiles/round6_bench_kernel_stats_serial.csv"
