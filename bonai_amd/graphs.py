@@ -67,6 +67,13 @@ class FeatureGraphs:
         registry knows every conv of the section (step >= 2).  Nothing executes during capture; the caller replays afterwards."""
         tr, m = self.tr, self.model
         dev = img.device
+        bb = getattr(m, 'backbone', None)
+        if getattr(bb, 'frozen_stages', 0) < 0 and any(p.requires_grad for p in (bb.conv1.weight, bb.bn1.weight, bb.bn1.bias)):
+            # The trainable stem packs its weights in the call and hands its gradients to autograd's accumulation, not to the
+            # arena sink the backward graph is built around; replaying it has not been validated, so it is refused (the trainer
+            # then stays on eager launches) rather than risk a replay on stale packed weights.
+            raise K.L.LoftHipError('hipGraph capture does not cover a trainable ResNet stem (frozen_stages < 0): '
+                                   'run with graph_features=False, or freeze the stem (frozen_stages >= 0)')
         self.static_img = torch.empty_like(img)
         self.static_img.copy_(img)
         self.token = torch.zeros(1, device=dev, requires_grad=True)

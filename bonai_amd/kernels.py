@@ -1213,6 +1213,26 @@ def stem7x7_mfma(img, w, scale, shift, packed=None):
     return out
 
 
+def stem7x7_pool_wgrad(img, y, gp):
+    """Backward of maxpool3x3s2(stem7x7(img)) w.r.t. the BN-folded stem weight, one launch.  img fp32 NCHW [B,3,H,W]; y = the
+    stem output before the pool and gp = the gradient of the pooled map, channels_last, both fp32 (parity mode) or both the
+    library's 16-bit type -> (dwp fp32 [49,64,3] in the tap packing fold_unpack_bwd consumes, db fp32 [64])."""
+    lib = L.load()
+    img = img.float().contiguous()
+    y, gp = _nhwc(y), _nhwc(gp)
+    L.dev_check(img, y, gp)
+    B, _, H, W = img.shape
+    Hy, Wy = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    if y.dtype != gp.dtype or tuple(y.shape) != (B, 64, Hy, Wy) or tuple(gp.shape) != (B, 64, (Hy - 1) // 2 + 1, (Wy - 1) // 2 + 1):
+        raise L.LoftHipError(f'stem7x7_pool_wgrad: y {tuple(y.shape)} {y.dtype} / gp {tuple(gp.shape)} {gp.dtype} do not belong '
+                             f'to an image of {tuple(img.shape)}')
+    dwp = torch.zeros(49, 64, 3, dtype=torch.float32, device=img.device)
+    db = torch.zeros(64, dtype=torch.float32, device=img.device)
+    L.check(lib.loft_stem7x7_pool_wgrad(L.ptr(img), L.ptr(y), L.ptr(gp), L.ptr(dwp), L.ptr(db), L.dtype_code(y), B, H, W,
+                                        L.stream()), 'loft_stem7x7_pool_wgrad')
+    return dwp, db
+
+
 def cast_bf16(x_f32):
     lib = L.load()
     L.dev_check(x_f32)

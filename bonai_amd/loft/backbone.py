@@ -167,11 +167,8 @@ class ResNet(nn.Module):
         self._freeze_stages()
 
     def _freeze_stages(self):
-        """resnet.py:573-589.  frozen_stages < 0 (a trainable stem) is not built: the stem kernels have no backward, and its
-        parameters would sit in the optimiser arena receiving weight decay with a zero gradient (configs/loft_foa use 1)."""
-        if self.frozen_stages < 0:
-            raise NotImplementedError('ResNet(frozen_stages=-1): the 7x7 stem has no weight-gradient kernel; use frozen_stages >= 0 '
-                                      '(configs/_base_/models/bonai_loft_foa_r50_fpn_basic.py:24 sets 1)')
+        """resnet.py:573-589.  frozen_stages < 0: nothing is frozen -- conv1 and bn1's gamma / beta train too (norm_eval still
+        fixes every BN's statistics); the stem then runs as nn.stem7x7_pool, whose backward is loft_stem7x7_pool_wgrad."""
         if self.frozen_stages >= 0:
             for p in list(self.conv1.parameters()) + list(self.bn1.parameters()):
                 p.requires_grad = False
@@ -202,7 +199,12 @@ class ResNet(nn.Module):
 
     def forward(self, img):
         """img fp32 NCHW [B,3,H,W] -> tuple of bf16 NHWC-in-memory maps (C2..C5)."""
-        with torch.no_grad():                               # frozen stem (frozen_stages >= 0, enforced in _freeze_stages)
+        f32 = getattr(self, 'compute_dtype', None) == torch.float32
+        if torch.is_grad_enabled() and (self.conv1.weight.requires_grad or self.bn1.weight.requires_grad
+                                        or self.bn1.bias.requires_grad):
+            # trainable stem (frozen_stages < 0): one autograd node, current weights packed in the call
+            return self._stages(F2.stem7x7_pool(img, self.conv1.weight, self.bn1, torch.float32 if f32 else K.L.act16()))
+        with torch.no_grad():                               # frozen stem (frozen_stages >= 0), or nothing is differentiated
             if getattr(self, 'compute_dtype', None) == torch.float32:   # fp32 parity mode (else: the library's 16-bit type)
                 scale, shift = self.bn1.fold()
                 x = K.stem7x7_bn_relu(img, self.conv1.weight, scale, shift, out_dtype=torch.float32)
@@ -219,6 +221,10 @@ class ResNet(nn.Module):
                         F2._pack_cache_put(key, srcs, packed)
                 x = K.stem7x7_mfma(img, self.conv1.weight, None, None, packed=packed)
             x = K.maxpool3x3s2(x)
+        return self._stages(x)
+
+    def _stages(self, x):
+        """layer1..4 on the pooled stem output."""
         outs = []
         for i, name in enumerate(self.res_layers):
             layer = getattr(self, name)

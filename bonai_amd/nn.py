@@ -1067,6 +1067,43 @@ def stem3x3s2(img, w, bn, out_dtype=None):
     return _Stem3x3Fn.apply(img, w, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, out_dtype)
 
 
+class _Stem7x7PoolFn(torch.autograd.Function):
+    """maxpool3x3/2(relu(bn(conv7x7/2(img)))) of a TRAINABLE ResNet stem (frozen_stages < 0; resnet.py:628-631) as one node.
+
+    forward : the frozen stem's two launches (MFMA stem, or the fp32 stem in the parity mode; then the pool), on a packing of
+              the CURRENT weights made in this call -- never the per-parameter pack cache, which is for frozen parameters.
+    backward: loft_stem7x7_pool_wgrad (pool argmax recomputed from the saved y, ReLU mask, weight gradient: one launch, the
+              pre-activation gradient stays in LDS) -> loft_fold_unpack_bwd (d conv1.weight, d bn1.weight, d bn1.bias).
+    The image gets no gradient.  y [B,64,H/2,W/2] is held until the backward."""
+
+    @staticmethod
+    def forward(ctx, img, w, gamma, beta, mean, var, eps, out_dtype):
+        scale = gamma * torch.rsqrt(var + eps)
+        shift = beta - mean * scale
+        if out_dtype == torch.float32:
+            y = K.stem7x7_bn_relu(img, w, scale, shift, out_dtype=torch.float32)
+        else:
+            y = K.stem7x7_mfma(img, w, scale, shift)
+        p = K.maxpool3x3s2(y)
+        ctx.save_for_backward(img, w, gamma, beta, mean, var, y)
+        ctx.eps = eps
+        return _begin_uses(p)
+
+    @staticmethod
+    def backward(ctx, g):
+        img, w, gamma, beta, mean, var, y = ctx.saved_tensors
+        g = to_nhwc(g)
+        if g.dtype != y.dtype:
+            g = g.to(y.dtype)
+        dwp, db = K.stem7x7_pool_wgrad(img, y, g)
+        dw, dg, dbeta = K.fold_unpack_bwd(dwp, db, w, (gamma, beta, mean, var), ctx.eps)
+        return None, dw, dg, dbeta, None, None, None, None
+
+
+def stem7x7_pool(img, w, bn, out_dtype=None):
+    return _Stem7x7PoolFn.apply(img, w, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, out_dtype or K.L.act16())
+
+
 # ------------------------------------------------------------------ sparse backward of the RPN head
 
 def _as_img(t2d):

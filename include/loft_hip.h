@@ -579,6 +579,15 @@ int loft_stem3x3s2_bn_relu(const float* img, const float* w, const float* scale,
                            int B, int H, int W, void* stream);
 int loft_stem3x3s2_wgrad(const float* img, const void* g, const void* y, float* dwp, float* db, int dtype, int B, int H, int W,
                          void* stream);
+/* loft_stem7x7_pool_wgrad: backward of the trainable ResNet stem, maxpool3x3/2(relu(bn(conv7x7/2(img)))), in one launch
+ *   (resnet.py:628-631; frozen_stages < 0).  img fp32 NCHW [B,3,H,W]; y = the saved stem output before the pool, NHWC
+ *   [B,H/2,W/2,64]; gp = gradient of the pooled map, NHWC [B,H/4,W/4,64]; both fp32 (dtype LOFT_F32, plain fp32 FMA) or the
+ *   build's 16-bit type (matrix cores, fp32 accumulate).  dwp fp32 [49][64][3] += gradient of the BN-folded weight, db fp32
+ *   [64] += gradient of the BN shift; the caller zeroes both and feeds them to loft_fold_unpack_bwd.  The pool's argmax is
+ *   recomputed from y with F.max_pool2d's rule (first maximum in (ky, kx) order, padding never wins); the pre-activation
+ *   gradient [B,H/2,W/2,64] is built per tile in LDS and never written to memory.  Any H, W >= 1, B >= 1. */
+int loft_stem7x7_pool_wgrad(const float* img, const void* y, const void* gp, float* dwp, float* db, int dtype, int B, int H,
+                            int W, void* stream);
 
 /* ---- modulated deformable convolution (DCNv2) sampling ------------------------------------------
  * Replaces mmcv.ops.ModulatedDeformConv2dPack / modulated_deform_conv2d [mmcv==1.0.5, not in tree] at the call sites
