@@ -701,20 +701,21 @@ LOFT_EXPORT int loft_sumsq_f32(const float* g, int64_t n, float* out, void* stre
     return 0;
 }
 
+// The update body shared by sgd_kernel and sgd_scaled_kernel (so the two cannot drift).  stride / t0: the grid-stride loop's step and
+// this lane's first index, computed by the kernel itself (the launch geometry is read where the compiler knows it is uniform).
 // p, g, m: flat fp32 [n].  gnorm_sq: device scalar (sum of squares of ALL grads, after all-reduce
 // averaging).  clip = max_norm / (norm + 1e-6) if norm > max_norm else 1 (torch clip_grad_norm_).
 // torch.optim.SGD: d = g*clip + wd*p ; m = mu*m + d ; p -= lr*m   (first step m = d is the caller's
 // business: start from m = 0 and it is identical).
-__global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, long n,
-                           const float* __restrict__ gnorm_sq, float max_norm, float lr, float mu, float wd,
-                           float gscale) {
+__device__ __forceinline__ void sgd_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, long n,
+                                           float gnorm_sq, float max_norm, float lr, float mu, float wd, float gscale,
+                                           const long stride, const long t0) {
     float clip = 1.f;
     if (max_norm > 0.f) {
-        const float norm = sqrtf(*gnorm_sq) * gscale;
+        const float norm = sqrtf(gnorm_sq) * gscale;
         if (norm > max_norm) clip = max_norm / (norm + 1e-6f);
     }
     const float s = clip * gscale;
-    const long stride = (long)gridDim.x * blockDim.x, t0 = blockIdx.x * (long)blockDim.x + threadIdx.x;
     // 16-byte accesses on the aligned body (five HBM streams), scalar tail
     const bool al = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m)) & 15) == 0;
     const long n4 = al ? n >> 2 : 0;
@@ -749,11 +750,79 @@ __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, f
         p[i] = pv - lr * mv;
     }
 }
+__global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, long n,
+                           const float* __restrict__ gnorm_sq, float max_norm, float lr, float mu, float wd,
+                           float gscale) {
+    sgd_update(p, g, m, n, *gnorm_sq, max_norm, lr, mu, wd, gscale, (long)gridDim.x * blockDim.x,
+               blockIdx.x * (long)blockDim.x + threadIdx.x);
+}
 LOFT_EXPORT int loft_sgd_momentum_f32(float* p, const float* g, float* m, int64_t n, const float* gnorm_sq, float max_norm,
                                       float lr, float momentum, float weight_decay, float grad_scale, void* stream) {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(sgd_kernel, ew_grid(n / 4), dim3(256), 0, (hipStream_t)stream, p, g, m, (long)n, gnorm_sq, max_norm, lr,
                        momentum, weight_decay, grad_scale);
+    LOFT_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- dynamic loss scaling (binary16 training): the decision is taken on the device, the host never reads a gradient ----
+// state: LOFT_LS_WORDS 32-bit words (include/loft_hip.h).  A gradient that overflowed in binary16 is +-inf or NaN in the arena; its
+// square is +inf or NaN and squares cannot cancel, so sumsq_kernel's sum is non-finite exactly when some gradient is (or when the
+// squares themselves overflow fp32, which is treated as an overflow too).  The test is on the bit pattern -- exponent field all
+// ones -- so it holds under any floating-point compiler flag.
+__device__ __forceinline__ bool ls_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
+
+// sgd_kernel with grad_scale = inv_world / scale (scale read from the state) and the WHOLE update skipped on overflow: no
+// workgroup writes p or m.  The state is only read here; loss_scale_update_kernel, the next launch on the stream, writes it.
+__global__ void sgd_scaled_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, long n,
+                                  const float* __restrict__ gnorm_sq, float max_norm, float lr, float mu, float wd,
+                                  float inv_world, const float* __restrict__ state) {
+    const float ss = *gnorm_sq;
+    if (ls_nonfinite(ss)) return;
+    sgd_update(p, g, m, n, ss, max_norm, lr, mu, wd, inv_world * (1.0f / state[LOFT_LS_SCALE]), (long)gridDim.x * blockDim.x,
+               blockIdx.x * (long)blockDim.x + threadIdx.x);
+}
+LOFT_EXPORT int loft_sgd_momentum_scaled_f32(float* p, const float* g, float* m, int64_t n, const float* gnorm_sq,
+                                             float max_norm, float lr, float momentum, float weight_decay, float inv_world,
+                                             const void* state, void* stream) {
+    if (n <= 0) return 0;
+    if (!state || !gnorm_sq) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(sgd_scaled_kernel, ew_grid(n / 4), dim3(256), 0, (hipStream_t)stream, p, g, m, (long)n, gnorm_sq, max_norm,
+                       lr, momentum, weight_decay, inv_world, (const float*)state);
+    LOFT_LAUNCH_CHECK();
+    return 0;
+}
+
+// torch.amp.GradScaler's update (aten _amp_update_scale_) plus the clamps, one lane.  Plain stores from a vector lane.
+__global__ void loss_scale_update_kernel(uint32_t* __restrict__ state, const float* __restrict__ gnorm_sq, float inv_world,
+                                         float growth, float backoff, int interval, float min_scale, float max_scale) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const float ss = *gnorm_sq;
+    const float scale = __uint_as_float(state[LOFT_LS_SCALE]);
+    const bool overflow = ls_nonfinite(ss);
+    float next = scale;
+    uint32_t good = state[LOFT_LS_GOOD_STEPS], skipped = state[LOFT_LS_SKIPPED];
+    if (overflow) {
+        next = fmaxf(scale * backoff, min_scale);
+        good = 0;
+        skipped += 1;
+    } else if (++good == (uint32_t)interval) {
+        next = fminf(scale * growth, max_scale);
+        good = 0;
+    }
+    state[LOFT_LS_SCALE] = __float_as_uint(next);
+    state[LOFT_LS_GOOD_STEPS] = good;
+    state[LOFT_LS_SKIPPED] = skipped;
+    state[LOFT_LS_LAST_SKIPPED] = overflow ? 1u : 0u;
+    state[LOFT_LS_GRAD_NORM] = __float_as_uint(sqrtf(ss) * inv_world / scale);     // (the scale in force for THIS step)
+}
+LOFT_EXPORT int loft_loss_scale_update(void* state, const float* gnorm_sq, float inv_world, float growth_factor,
+                                       float backoff_factor, int growth_interval, float min_scale, float max_scale, void* stream) {
+    if (!state || !gnorm_sq || growth_interval < 1 || !(backoff_factor > 0.f && backoff_factor < 1.f && growth_factor > 1.f) ||
+        !(min_scale > 0.f && min_scale <= max_scale))
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (uint32_t*)state, gnorm_sq, inv_world,
+                       growth_factor, backoff_factor, growth_interval, min_scale, max_scale);
     LOFT_LAUNCH_CHECK();
     return 0;
 }

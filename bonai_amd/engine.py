@@ -21,6 +21,7 @@ import torch.distributed as dist
 
 from . import kernels as K
 from .debug import DBG
+from .loss_scale import parse_loss_scale
 
 
 class FlatArena:
@@ -298,7 +299,12 @@ class Trainer:
         """loss_scale: the static scale of the reference's Fp16OptimizerHook (``fp16 = dict(loss_scale=512.)``,
         mmdet/core/fp16/hooks.py:64-96): the loss is multiplied before backward and the gradients are divided again inside
         the fused clip + SGD kernel (after the all-reduce, before the norm), exactly the hook's order.  bf16 activations have
-        fp32's exponent range, so the scale is not needed for range here; it is honoured for runner parity."""
+        fp32's exponent range, so the scale is not needed for range here; it is honoured for runner parity.
+
+        ``'dynamic'`` or a dict (bonai_amd/loss_scale.py: init_scale, growth_factor, backoff_factor, growth_interval, min_scale,
+        max_scale) selects the dynamic scaler -- an extension, the reference's hook is static-only -- with torch.amp.GradScaler's
+        rule: a step whose gradients are not finite is skipped and the scale backs off, growth_interval clean steps in a row grow
+        it again.  Scale, counters and the decision live on the device (``scale_state``); the step loop still never reads back."""
         self.model = model
         # graph_features: backbone + neck forward and backward as two hipGraphs, recorded at the third step and replayed from
         # then on (bonai_amd/graphs.py); fixed-size batches only.  Capture failures fall back to eager launches, loudly.
@@ -307,11 +313,21 @@ class Trainer:
         self._unpack_stream = None
         self._steps_run = 0          # steps THIS trainer has run (a resumed trainer starts at iter > 0 with an empty prepack registry)
         self.lr, self.mu, self.wd, self.max_norm = lr, momentum, weight_decay, max_norm
-        self.loss_scale = float(loss_scale)
+        mode, parsed = parse_loss_scale(loss_scale)
+        # static: the float, used exactly as before.  dynamic: None -- the scale is a device value, see loss_scale_state()
+        self.loss_scale = parsed if mode == 'static' else None
+        self.scaler = parsed if mode == 'dynamic' else None
         self.arena = FlatArena(model)
         self.reducer = BucketedAllReduce(self.arena, bucket_bytes)
         self.world = dist.get_world_size() if self.reducer.enabled else 1
         self.gnorm_sq = torch.zeros(1, dtype=torch.float32, device=self.arena.data.device)
+        self.scale_state = self._scale = None
+        if self.scaler is not None:
+            # graph_features: the scale multiplies the loss OUTSIDE the captured backbone + neck; the backward graph's only inputs
+            # are the static gradient maps FeatureGraphs._run_backward copies the live (scaled) gradients into before every replay,
+            # so a replay sees the current scale and nothing of it is baked into a graph -- the combination is allowed.
+            self.scale_state = K.loss_scale_state_pack(self.scaler['init_scale']).to(self.arena.data.device)
+            self._scale = self.scale_state[K.LS_SCALE]      # 0-dim VIEW of the state's scale: the loss's multiplier
         self.iter = 0
         self.prepack = K.PrepackRegistry()
         # kernels accumulate weight / BN gradients straight into the arena slots (bonai_amd.nn.GRAD_SINK); the callback
@@ -356,7 +372,19 @@ class Trainer:
                      params=list(range(len(idx))))
         # sampler_calls: the RandomSampler kernel's draws are a function of (torch.initial_seed(), call count); a resumed run
         # continues the uninterrupted run's sequence only if the count travels with the optimizer state
-        return dict(state=state, param_groups=[group], iter=self.iter, sampler_calls=int(K._SAMPLE_CALLS[0]))
+        sd = dict(state=state, param_groups=[group], iter=self.iter, sampler_calls=int(K._SAMPLE_CALLS[0]))
+        if self.scaler is not None:                       # (dynamic mode only: the static layout is what the reference stores)
+            sd['loss_scaler'] = self.loss_scale_state()
+        return sd
+
+    def loss_scale_state(self):
+        """dict(scale, good_steps, skipped, last_skipped, grad_norm) -- the ONLY call of the loss scaler that synchronises with the
+        device (one device-to-host copy).  grad_norm is the unscaled pre-clip gradient norm of the last step (what mmcv's
+        OptimizerHook logs), non-finite when that step was skipped.  Static mode: the static scale, nothing is ever skipped."""
+        if self.scaler is not None:
+            return K.loss_scale_state_unpack(self.scale_state)
+        norm = float(self.gnorm_sq.cpu()[0]) ** 0.5 / (self.world * self.loss_scale)
+        return dict(scale=self.loss_scale, good_steps=self._steps_run, skipped=0, last_skipped=False, grad_norm=norm)
 
     def load_optimizer_state(self, sd):
         """Inverse of optimizer_state_dict (also accepts a reference checkpoint's torch SGD state: state index i is the i-th
@@ -388,6 +416,8 @@ class Trainer:
         self.iter = int(sd.get('iter', self.iter))
         if 'sampler_calls' in sd:
             K._SAMPLE_CALLS[0] = int(sd['sampler_calls'])
+        if self.scaler is not None and sd.get('loss_scaler') is not None:      # (absent in a reference SGD state: keep the scale)
+            self.scale_state.copy_(K.loss_scale_state_pack(**sd['loss_scaler']))
 
     def train_step(self, data, lr=None):
         """One full optimisation step: forward, losses, backward, gradient all-reduce, clip, SGD."""
@@ -441,7 +471,12 @@ class Trainer:
                     self._wgrad_stream = torch.cuda.Stream()
                 F2.WGRAD_STREAM = self._wgrad_stream
         try:
-            (out['loss'] if self.loss_scale == 1.0 else out['loss'] * self.loss_scale).backward()
+            if self.scaler is None:
+                (out['loss'] if self.loss_scale == 1.0 else out['loss'] * self.loss_scale).backward()
+            else:
+                # The scale enters ONLY here, as the backward seed: forward, samplers and NMS never see it, and no backward
+                # kernel branches on gradient values, so an overflow can only put inf / NaN into gradient VALUES.
+                (out['loss'] * self._scale).backward()
             if F2.UNPACK_Q is not None:
                 F2.UNPACK_Q.flush()
         finally:
@@ -457,8 +492,19 @@ class Trainer:
         self.reducer.finish()
         self.gnorm_sq.zero_()
         K.sumsq_(self.arena.grad, self.gnorm_sq)
-        K.sgd_momentum_(self.arena.data, self.arena.grad, self.arena.momentum, self.gnorm_sq, self.max_norm,
-                        self.lr if lr is None else lr, self.mu, self.wd, grad_scale=1.0 / (self.world * self.loss_scale))
+        if self.scaler is None:
+            K.sgd_momentum_(self.arena.data, self.arena.grad, self.arena.momentum, self.gnorm_sq, self.max_norm,
+                            self.lr if lr is None else lr, self.mu, self.wd, grad_scale=1.0 / (self.world * self.loss_scale))
+        else:
+            # Skip-or-apply and the next scale are decided on the device from gnorm_sq.  Data parallelism: every rank computes
+            # gnorm_sq over the SAME all-reduced arena and holds the same scale state, so all ranks take the same decision
+            # without exchanging it.  The update runs after the SGD launch: no SGD workgroup reads a half-updated scale.
+            c = self.scaler
+            K.sgd_momentum_scaled_(self.arena.data, self.arena.grad, self.arena.momentum, self.gnorm_sq, self.max_norm,
+                                   self.lr if lr is None else lr, self.mu, self.wd, 1.0 / self.world, self.scale_state)
+            K.loss_scale_update_(self.scale_state, self.gnorm_sq, 1.0 / self.world, c['growth_factor'], c['backoff_factor'],
+                                 c['growth_interval'], c['min_scale'], c['max_scale'])
+        # (a skipped step advances iter too: the learning-rate schedule does not stall, as in mmcv and torch)
         self.iter += 1
         self._steps_run += 1
         return out

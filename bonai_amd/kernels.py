@@ -1265,6 +1265,53 @@ def sgd_momentum_(p, g, m, gnorm_sq, max_norm, lr, momentum, weight_decay, grad_
                                       c_float(grad_scale), L.stream()), 'loft_sgd_momentum_f32')
 
 
+# ---- dynamic loss scaling: the device-side state of include/loft_hip.h (LOFT_LS_*), held as a float32 tensor of LS_WORDS words
+# whose integer fields are read through an int32 view
+LS_SCALE, LS_GOOD_STEPS, LS_SKIPPED, LS_LAST_SKIPPED, LS_GRAD_NORM, LS_WORDS = 0, 1, 2, 3, 4, 8
+
+
+def loss_scale_state_pack(scale, good_steps=0, skipped=0, last_skipped=False, grad_norm=0.0):
+    """-> the state as a CPU float32 tensor [LS_WORDS] (copy it to the device / into the trainer's state buffer)."""
+    st = torch.zeros(LS_WORDS, dtype=torch.float32)
+    st[LS_SCALE], st[LS_GRAD_NORM] = float(scale), float(grad_norm)
+    words = st.view(torch.int32)
+    words[LS_GOOD_STEPS], words[LS_SKIPPED], words[LS_LAST_SKIPPED] = int(good_steps), int(skipped), int(bool(last_skipped))
+    return st
+
+
+def loss_scale_state_unpack(state):
+    """The state tensor (any device: ONE copy to the host) -> dict(scale, good_steps, skipped, last_skipped, grad_norm)."""
+    st = state.detach().cpu()
+    words = st.view(torch.int32)
+    return dict(scale=float(st[LS_SCALE]), good_steps=int(words[LS_GOOD_STEPS]), skipped=int(words[LS_SKIPPED]),
+                last_skipped=bool(int(words[LS_LAST_SKIPPED])), grad_norm=float(st[LS_GRAD_NORM]))
+
+
+def _ls_state_check(state):
+    if state.dtype != torch.float32 or state.numel() != LS_WORDS or not state.is_contiguous():
+        raise L.LoftHipError(f'the loss-scaler state is a contiguous float32 tensor of {LS_WORDS} words')
+
+
+def sgd_momentum_scaled_(p, g, m, gnorm_sq, max_norm, lr, momentum, weight_decay, inv_world, state):
+    """sgd_momentum_ with grad_scale = inv_world / (the scale in ``state``), skipped entirely when ``gnorm_sq`` is not finite."""
+    lib = L.load()
+    L.dev_check(p, g, m, gnorm_sq, state)
+    _ls_state_check(state)
+    L.check(lib.loft_sgd_momentum_scaled_f32(L.ptr(p), L.ptr(g), L.ptr(m), c_int64(p.numel()), L.ptr(gnorm_sq),
+                                             c_float(max_norm), c_float(lr), c_float(momentum), c_float(weight_decay),
+                                             c_float(inv_world), L.ptr(state), L.stream()), 'loft_sgd_momentum_scaled_f32')
+
+
+def loss_scale_update_(state, gnorm_sq, inv_world, growth_factor, backoff_factor, growth_interval, min_scale, max_scale):
+    """GradScaler's update of the device-side state from ``gnorm_sq``; launch it after sgd_momentum_scaled_ on the same stream."""
+    lib = L.load()
+    L.dev_check(state, gnorm_sq)
+    _ls_state_check(state)
+    L.check(lib.loft_loss_scale_update(L.ptr(state), L.ptr(gnorm_sq), c_float(inv_world), c_float(growth_factor),
+                                       c_float(backoff_factor), c_int(int(growth_interval)), c_float(min_scale),
+                                       c_float(max_scale), L.stream()), 'loft_loss_scale_update')
+
+
 # ------------------------------------------------------------------ boxes / targets
 
 def iou_assign(boxes, nbox, gts, ngt, pos_thr, neg_thr, min_pos, low_quality=True):

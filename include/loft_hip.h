@@ -444,6 +444,31 @@ int loft_add_bf16(const void* a, const void* b, void* out, int64_t n, void* stre
 int loft_sumsq_f32(const float* g, int64_t n, float* out, void* stream);
 int loft_sgd_momentum_f32(float* p, const float* g, float* m, int64_t n, const float* gnorm_sq, float max_norm, float lr,
                           float momentum, float weight_decay, float grad_scale, void* stream);
+/* Dynamic loss scaling for binary16 training, decided on the device.  NOT in the reference, whose Fp16OptimizerHook
+ * (mmdet/core/fp16/hooks.py:64-96) has a static scale only: the rule is torch.amp.GradScaler's plus two clamps.
+ * state: LOFT_LS_WORDS 32-bit words in device memory, indexed by the LOFT_LS_* constants:
+ *   SCALE fp32 current scale | GOOD_STEPS uint32 consecutive clean steps | SKIPPED uint32 total skipped steps |
+ *   LAST_SKIPPED uint32 1 when the last step was skipped | GRAD_NORM fp32 last unscaled pre-clip gradient norm
+ *   (sqrt(*gnorm_sq) * inv_world / scale: what mmcv's OptimizerHook logs as grad_norm; non-finite as it stands on a skipped
+ *   step) | words 5-7 reserved, zero.
+ * sgd_momentum_scaled: loft_sgd_momentum_f32 (same update body) with grad_scale = inv_world * (1 / state[SCALE]); when
+ *   *gnorm_sq (from loft_sumsq_f32) is not finite -- exponent bits all ones: some gradient is +-inf / NaN, or the squares
+ *   overflow fp32 -- nothing is written to p or m.  It only reads the state.
+ * loss_scale_update: one launch AFTER sgd_momentum_scaled on the same stream (so no SGD workgroup sees a half-updated
+ *   scale).  Overflow: scale = max(scale * backoff_factor, min_scale), GOOD_STEPS = 0, SKIPPED += 1.  Otherwise
+ *   GOOD_STEPS += 1 and, when it equals growth_interval, scale = min(scale * growth_factor, max_scale), GOOD_STEPS = 0.
+ *   Writes LAST_SKIPPED and GRAD_NORM (with the scale that was in force for this step). */
+#define LOFT_LS_SCALE 0
+#define LOFT_LS_GOOD_STEPS 1
+#define LOFT_LS_SKIPPED 2
+#define LOFT_LS_LAST_SKIPPED 3
+#define LOFT_LS_GRAD_NORM 4
+#define LOFT_LS_WORDS 8
+int loft_sgd_momentum_scaled_f32(float* p, const float* g, float* m, int64_t n, const float* gnorm_sq, float max_norm,
+                                 float lr, float momentum, float weight_decay, float inv_world, const void* state,
+                                 void* stream);
+int loft_loss_scale_update(void* state, const float* gnorm_sq, float inv_world, float growth_factor, float backoff_factor,
+                           int growth_interval, float min_scale, float max_scale, void* stream);
 
 /* ---- box / target arithmetic (fp32 + integer) -------------------------------------------------
  * iou_assign: MaxIoUAssigner.assign (mmdet/core/bbox/assigners/max_iou_assigner.py:60-212 with

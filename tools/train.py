@@ -63,7 +63,8 @@ def main():
         dist.init_process_group(cfg.dist_params.get('backend', 'nccl'))
     torch.manual_seed(args.seed)
     from bonai_amd.checkpoint import load_checkpoint, save_checkpoint
-    if cfg.get('fp16'):                                    # Fp16OptimizerHook recipe: half activations, fp32 masters, static scale
+    if cfg.get('fp16'):                # Fp16OptimizerHook recipe: half activations, fp32 masters; loss_scale: a number (the reference's
+                                       # static scale), 'dynamic' or a dict (bonai_amd/loss_scale.py; --options fp16.loss_scale=dynamic)
         from bonai_amd import lib as L
         L.set_act16(torch.float16)
     if args.pretrained:
@@ -119,6 +120,9 @@ def main():
         if rank == 0 and (it + 1) % interval == 0:
             torch.cuda.synchronize()
             lv = ', '.join(f'{k}: {v:.4f}' for k, v in out['log_vars'].items())
+            if cfg.get('fp16'):                            # (log lines only: the one read-back of the loss scaler's device state)
+                ls = tr.loss_scale_state()
+                lv += f", loss_scale: {ls['scale']:g}, skipped: {ls['skipped']}, grad_norm: {ls['grad_norm']:.4f}"
             print(f'Epoch [{it // ipe + 1}][{it % ipe + 1}/{ipe}] time: {(time.time() - t0) / (it - start_iter + 1):.3f}, {lv}', flush=True)
     if args.work_dir and rank == 0:
         os.makedirs(args.work_dir, exist_ok=True)
