@@ -1581,13 +1581,15 @@ LOFT_EXPORT int loft_conv_wgrad_patch_bf16(const void* g, const void* x, float* 
 }
 
 
-int loft_launch_conv_wgrad_stream(const WgradArgs& a, dim3 grid, bool pm, hipStream_t s);     // conv_wgrad_pipe.hip
-int loft_launch_conv_wgrad_ring(const WgradArgs& a, dim3 grid, hipStream_t s);                 // conv_wgrad_pipe.hip
+// (conv_wgrad_pipe.hip; form_out != nullptr: *form_out = the LOFT_WGRAD_FORM_* code of the kernel they would launch, no launch)
+int loft_launch_conv_wgrad_stream(const WgradArgs& a, dim3 grid, bool pm, hipStream_t s, int* form_out);
+int loft_launch_conv_wgrad_ring(const WgradArgs& a, dim3 grid, hipStream_t s, int* form_out);
 
 // mode 0: launch, split-K combined with fp32 atomics into the zeroed dw.  mode 1: no launch, *nslots_out = the number of
 // split slots a partial-sum launch of this shape writes (0: this shape has no such form -- narrow channels, repeated or missing
 // weight taps, a tap without a valid row).  mode 2: launch, every workgroup STORES its tile into its split's slot of
-// dw = [group][nslots][T][Cout][Cin] (dw_gs = nslots * T * Cout * Cin); see WgradArgs::partial.
+// dw = [group][nslots][T][Cout][Cin] (dw_gs = nslots * T * Cout * Cin); see WgradArgs::partial.  mode 3: mode 0's path up to the
+// launch, which is not made: *nslots_out = the LOFT_WGRAD_FORM_* code of the kernel mode 0 launches (loft_conv_wgrad_form).
 // Operand planes of a weight-gradient launch (loft_conv_wgrad_planes): the launch's groups are `groups * nterms` virtual groups,
 // virtual group grp * nterms + p reads G plane gpl[p] / X plane xpl[p] of real group grp and adds into that group's dW.
 struct WgradPlanes {
@@ -1617,6 +1619,8 @@ static int wgrad_impl(const void* g, const void* x, float* dw, const void* zero_
         }
     }
     if (nslots_out) *nslots_out = 0;
+    int* const form_out = mode == 3 ? nslots_out : nullptr;      // mode 3: the out parameter carries the form code, ...
+    static_assert(LOFT_WGRAD_FORM_NONE == 0, "... and the zero stored above must read as 'nothing is launched'");
     if (mode == 2 && !slots_ok) return (int)hipErrorInvalidValue;
     WgradArgs a;
     a.pm_inc_ok = 0;
@@ -1660,7 +1664,7 @@ static int wgrad_impl(const void* g, const void* x, float* dw, const void* zero_
     a.g_gs = g_gs; a.x_gs = x_gs; a.dw_gs = dw_gs;
     a.db = db; a.db_tap = db ? db_tap : -1;
     const long M = (long)B * OH * OW;
-    if (M <= 0) return mode == 2 ? (int)hipErrorInvalidValue : 0;
+    if (M <= 0) return mode == 2 ? (int)hipErrorInvalidValue : 0;          // (mode 3: LOFT_WGRAD_FORM_NONE, set above)
     if (M > 0x7fffffffL) return (int)hipErrorInvalidValue;
     a.M = (int)M;
     fastdiv_setup((unsigned)(OH * OW), &a.ohw_mul, &a.ohw_sh);
@@ -1763,8 +1767,10 @@ static int wgrad_impl(const void* g, const void* x, float* dw, const void* zero_
             if (mode == 1) { if (nslots_out) *nslots_out = (slots_ok && every) ? maxns : 0; return 0; }
             if (mode == 2 && (!every || dw_gs != (int64_t)maxns * a.split_stride)) return (int)hipErrorInvalidValue;
             dim3 grid(tiles, groups, blk);
-            if (piped) return loft_launch_conv_wgrad_stream(a, grid, true, (hipStream_t)stream);
-            if (big) hipLaunchKernelGGL((conv_wgrad_kernel<256, 8, true>), grid, dim3(512), 0, (hipStream_t)stream, a);
+            if (piped) return loft_launch_conv_wgrad_stream(a, grid, true, (hipStream_t)stream, form_out);
+            const int form = big ? LOFT_WGRAD_FORM_T256_PM : LOFT_WGRAD_FORM_T128_PM;
+            if (form_out) { *form_out = form; return 0; }
+            if (form == LOFT_WGRAD_FORM_T256_PM) hipLaunchKernelGGL((conv_wgrad_kernel<256, 8, true>), grid, dim3(512), 0, (hipStream_t)stream, a);
             else hipLaunchKernelGGL((conv_wgrad_kernel<128, 4, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
             LOFT_LAUNCH_CHECK();
             return 0;
@@ -1776,22 +1782,26 @@ static int wgrad_impl(const void* g, const void* x, float* dw, const void* zero_
     if (mode == 1) { if (nslots_out) *nslots_out = slots_ok ? splits : 0; return 0; }
     if (mode == 2 && dw_gs != (int64_t)splits * a.split_stride) return (int)hipErrorInvalidValue;
     dim3 grid(tiles, T * groups, splits);
-    if (piped) return loft_launch_conv_wgrad_stream(a, grid, false, (hipStream_t)stream);
+    if (piped) return loft_launch_conv_wgrad_stream(a, grid, false, (hipStream_t)stream, form_out);
     if (narrow) {
         const bool samesize = gos == 1 && ss == 1 && GH == OH && GW == OW && XH == OH && XW == OW;
         bool same = samesize && OW >= 64;
         for (int t = 0; t < T; ++t) same = same && a.goy[t] == 0 && a.gox[t] == 0;
         const bool dense = samesize && T == 1 && a.goy[0] == 0 && a.gox[0] == 0 && a.dy[0] == 0 && a.dx[0] == 0;
-        if (dense) hipLaunchKernelGGL(conv_wgrad64_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, a);
-        else if (same) hipLaunchKernelGGL(conv_wgrad64_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, a);
+        const int form = dense ? LOFT_WGRAD_FORM_NARROW_DENSE : same ? LOFT_WGRAD_FORM_NARROW_SAME : LOFT_WGRAD_FORM_NARROW_GENERIC;
+        if (form_out) { *form_out = form; return 0; }
+        if (form == LOFT_WGRAD_FORM_NARROW_DENSE) hipLaunchKernelGGL(conv_wgrad64_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, a);
+        else if (form == LOFT_WGRAD_FORM_NARROW_SAME) hipLaunchKernelGGL(conv_wgrad64_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, a);
         else hipLaunchKernelGGL(conv_wgrad64_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, a);
     }
-    else if (big)
-        hipLaunchKernelGGL((conv_wgrad_kernel<256, 8>), grid, dim3(512), 0, (hipStream_t)stream, a);
-    else if (variant != LOFT_WGRAD_T128)
-        return loft_launch_conv_wgrad_ring(a, grid, (hipStream_t)stream);          // four-stage ring (conv_wgrad_pipe.hip)
-    else
-        hipLaunchKernelGGL((conv_wgrad_kernel<128, 4>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    else if (!big && variant != LOFT_WGRAD_T128)
+        return loft_launch_conv_wgrad_ring(a, grid, (hipStream_t)stream, form_out);          // four-stage ring (conv_wgrad_pipe.hip)
+    else {
+        const int form = big ? LOFT_WGRAD_FORM_T256 : LOFT_WGRAD_FORM_T128;
+        if (form_out) { *form_out = form; return 0; }
+        if (form == LOFT_WGRAD_FORM_T256) hipLaunchKernelGGL((conv_wgrad_kernel<256, 8>), grid, dim3(512), 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL((conv_wgrad_kernel<128, 4>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    }
     LOFT_LAUNCH_CHECK();
     return 0;
 }
@@ -1827,6 +1837,15 @@ LOFT_EXPORT int loft_conv_wgrad_slots(int B, int GH, int GW, int Cout, int XH, i
     const int e = wgrad_impl(nullptr, nullptr, nullptr, nullptr, B, GH, GW, Cout, XH, XW, Cin, OH, OW, gos, ss, T, goy_host,
                              gox_host, dy_host, dx_host, wt_host, groups, 0, 0, 0, splits, nullptr, -1, variant, nullptr, 1, &n);
     return e ? -e : n;
+}
+
+LOFT_EXPORT int loft_conv_wgrad_form(int B, int GH, int GW, int Cout, int XH, int XW, int Cin, int OH, int OW, int gos, int ss,
+                                     int T, const int* goy_host, const int* gox_host, const int* dy_host, const int* dx_host,
+                                     const int* wt_host, int groups, int splits, int variant) {
+    int form = LOFT_WGRAD_FORM_NONE;
+    const int e = wgrad_impl(nullptr, nullptr, nullptr, nullptr, B, GH, GW, Cout, XH, XW, Cin, OH, OW, gos, ss, T, goy_host,
+                             gox_host, dy_host, dx_host, wt_host, groups, 0, 0, 0, splits, nullptr, -1, variant, nullptr, 3, &form);
+    return e ? -e : form;
 }
 
 LOFT_EXPORT int loft_conv_wgrad_bf16_slots(const void* g, const void* x, float* dw_slots, const void* zero_page, int B, int GH,

@@ -380,18 +380,24 @@ __global__ __launch_bounds__(512) void conv_wgrad_stream_kernel(const WgradArgs 
 }
 
 // host side: launched from loft_conv_wgrad_bf16_v (conv_mfma.hip).  Requires Cout % 256 == 0 and Cin % 256 == 0.
-int loft_launch_conv_wgrad_stream(const WgradArgs& a, dim3 grid, bool pm, hipStream_t s) {
+// form_out (loft_conv_wgrad_form): the LOFT_WGRAD_FORM_* code of the kernel chosen below, and nothing is launched.
+int loft_launch_conv_wgrad_stream(const WgradArgs& a, dim3 grid, bool pm, hipStream_t s, int* form_out) {
     const bool samesize = a.gos == 1 && a.ss == 1 && a.GH == a.OH && a.GW == a.OW && a.XH == a.OH && a.XW == a.OW;
     bool same = samesize && a.OW >= 64;
     for (int t = 0; t < a.T; ++t) same = same && a.goy[t] == 0 && a.gox[t] == 0;
     const bool dense = samesize && a.T == 1 && a.goy[0] == 0 && a.gox[0] == 0 && a.dy[0] == 0 && a.dx[0] == 0;
     bool inc = pm && a.pm_inc_ok;
     for (int t = 0; t < a.T && inc; ++t) inc = a.pm_blk0[t + 1] == a.pm_blk0[t] || a.pm_pps[t] >= 64;
-    if (pm && inc) hipLaunchKernelGGL(conv_wgrad_stream_kernel<1>, grid, dim3(512), 0, s, a);
-    else if (pm) hipLaunchKernelGGL(conv_wgrad_stream_kernel<4>, grid, dim3(512), 0, s, a);
-    else if (dense) hipLaunchKernelGGL(conv_wgrad_stream_kernel<2>, grid, dim3(512), 0, s, a);
-    else if (same) hipLaunchKernelGGL(conv_wgrad_stream_kernel<3>, grid, dim3(512), 0, s, a);
-    else hipLaunchKernelGGL(conv_wgrad_stream_kernel<0>, grid, dim3(512), 0, s, a);
+    const int form = (pm && inc) ? LOFT_WGRAD_FORM_STREAM_PM_INC : pm ? LOFT_WGRAD_FORM_STREAM_PM : dense ? LOFT_WGRAD_FORM_STREAM_DENSE
+                     : same ? LOFT_WGRAD_FORM_STREAM_SAME : LOFT_WGRAD_FORM_STREAM_GENERIC;
+    if (form_out) { *form_out = form; return 0; }
+    switch (form) {
+    case LOFT_WGRAD_FORM_STREAM_PM_INC: hipLaunchKernelGGL(conv_wgrad_stream_kernel<1>, grid, dim3(512), 0, s, a); break;
+    case LOFT_WGRAD_FORM_STREAM_PM: hipLaunchKernelGGL(conv_wgrad_stream_kernel<4>, grid, dim3(512), 0, s, a); break;
+    case LOFT_WGRAD_FORM_STREAM_DENSE: hipLaunchKernelGGL(conv_wgrad_stream_kernel<2>, grid, dim3(512), 0, s, a); break;
+    case LOFT_WGRAD_FORM_STREAM_SAME: hipLaunchKernelGGL(conv_wgrad_stream_kernel<3>, grid, dim3(512), 0, s, a); break;
+    default: hipLaunchKernelGGL(conv_wgrad_stream_kernel<0>, grid, dim3(512), 0, s, a); break;
+    }
     LOFT_LAUNCH_CHECK();
     return 0;
 }
@@ -615,14 +621,18 @@ __global__ __launch_bounds__(256) void conv_wgrad_ring_kernel(const WgradArgs a)
         }
 }
 
-int loft_launch_conv_wgrad_ring(const WgradArgs& a, dim3 grid, hipStream_t s) {
+int loft_launch_conv_wgrad_ring(const WgradArgs& a, dim3 grid, hipStream_t s, int* form_out) {
     const bool dense = a.T == 1 && a.gos == 1 && a.ss == 1 && a.goy[0] == 0 && a.gox[0] == 0 && a.dy[0] == 0 && a.dx[0] == 0 &&
                        a.GH == a.OH && a.GW == a.OW && a.XH == a.OH && a.XW == a.OW;
     bool same = a.gos == 1 && a.ss == 1 && a.GH == a.OH && a.GW == a.OW && a.XH == a.OH && a.XW == a.OW && a.OW >= 32;
     for (int t = 0; t < a.T; ++t) same = same && a.goy[t] == 0 && a.gox[t] == 0;
-    if (dense) hipLaunchKernelGGL(conv_wgrad_ring_kernel<1>, grid, dim3(256), 0, s, a);
-    else if (same) hipLaunchKernelGGL(conv_wgrad_ring_kernel<2>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(conv_wgrad_ring_kernel<0>, grid, dim3(256), 0, s, a);
+    const int form = dense ? LOFT_WGRAD_FORM_RING_DENSE : same ? LOFT_WGRAD_FORM_RING_SAME : LOFT_WGRAD_FORM_RING_GENERIC;
+    if (form_out) { *form_out = form; return 0; }
+    switch (form) {
+    case LOFT_WGRAD_FORM_RING_DENSE: hipLaunchKernelGGL(conv_wgrad_ring_kernel<1>, grid, dim3(256), 0, s, a); break;
+    case LOFT_WGRAD_FORM_RING_SAME: hipLaunchKernelGGL(conv_wgrad_ring_kernel<2>, grid, dim3(256), 0, s, a); break;
+    default: hipLaunchKernelGGL(conv_wgrad_ring_kernel<0>, grid, dim3(256), 0, s, a); break;
+    }
     LOFT_LAUNCH_CHECK();
     return 0;
 }

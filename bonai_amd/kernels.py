@@ -1051,6 +1051,28 @@ def conv_wgrad(g, x, B, GH, GW, Cout, XH, XW, Cin, OH, OW, taps, n_wtaps, gos=1,
     return dw
 
 
+# LOFT_WGRAD_FORM_*: the kernel a weight-gradient launch takes (conv_wgrad_form)
+WGRAD_FORM_NONE = 0
+(WGRAD_FORM_T128, WGRAD_FORM_T128_PM, WGRAD_FORM_T256, WGRAD_FORM_T256_PM, WGRAD_FORM_RING_GENERIC, WGRAD_FORM_RING_DENSE,
+ WGRAD_FORM_RING_SAME, WGRAD_FORM_STREAM_GENERIC, WGRAD_FORM_STREAM_PM_INC, WGRAD_FORM_STREAM_DENSE, WGRAD_FORM_STREAM_SAME,
+ WGRAD_FORM_STREAM_PM, WGRAD_FORM_NARROW_GENERIC, WGRAD_FORM_NARROW_DENSE, WGRAD_FORM_NARROW_SAME) = range(1, 16)
+
+
+def conv_wgrad_form(B, GH, GW, Cout, XH, XW, Cin, OH, OW, taps, gos=1, ss=1, groups=1, splits=0, variant=None):
+    """The WGRAD_FORM_* code of the kernel conv_wgrad launches for 16-bit operands of this geometry (taps as there; variant: a
+    WGRAD_* code, default the current WGRAD_VARIANT).  Asks the library's launch path (loft_conv_wgrad_form); touches no device.
+    (Not seen from here: the patch kernel, which conv_wgrad itself picks for narrow channels on large maps.)"""
+    lib = L.load()
+    A = lambda i: L.arr(c_int, [t[i] for t in taps])
+    if variant is None:
+        variant = _wgrad_variant(groups, B, OH, OW, Cin, Cout, len(taps), ss, gos)
+    f = lib.loft_conv_wgrad_form(B, GH, GW, Cout, XH, XW, Cin, OH, OW, gos, ss, len(taps), A(0), A(1), A(2), A(3), A(4), groups,
+                                 splits, int(variant))
+    if f < 0:
+        L.check(-f, 'loft_conv_wgrad_form')
+    return f
+
+
 def conv2d_wgrad(g, x, R, S, stride=1, pad=0, groups=1, splits=0, with_bias=False, slots_ok=False):
     """-> fp32 [G, R*S, Cout, Cin] (packed layout; see unpack_dw); with_bias: also -> fp32 [G, Cout] bias gradient.
     slots_ok: see conv_wgrad (-> possibly [G, S, R*S, Cout, Cin])."""

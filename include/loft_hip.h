@@ -388,6 +388,28 @@ int loft_conv_wgrad_bf16_v(const void* g, const void* x, float* dw, const void* 
 int loft_conv_wgrad_slots(int B, int GH, int GW, int Cout, int XH, int XW, int Cin, int OH, int OW, int gos, int ss, int T,
                           const int* goy_host, const int* gox_host, const int* dy_host, const int* dx_host, const int* wt_host,
                           int groups, int splits, int variant);
+/* Which kernel loft_conv_wgrad_bf16_v (and, the split-K mode aside, loft_conv_wgrad_bf16_slots) launches for these arguments: the
+ * launch path itself, stopped before the launch -- no device is touched.  -> a LOFT_WGRAD_FORM_* code (tile family and
+ * sub-form), or -hipError_t for arguments the launch rejects.  For tests: a shape written for one form must keep reaching it. */
+#define LOFT_WGRAD_FORM_NONE 0            /* nothing is launched (no pixel, or no tap of a RoI map has a valid row) */
+#define LOFT_WGRAD_FORM_T128 1            /* conv_wgrad_kernel<128,4> */
+#define LOFT_WGRAD_FORM_T128_PM 2         /* conv_wgrad_kernel<128,4,true>: valid rows only (RoI maps) */
+#define LOFT_WGRAD_FORM_T256 3            /* conv_wgrad_kernel<256,8> */
+#define LOFT_WGRAD_FORM_T256_PM 4         /* conv_wgrad_kernel<256,8,true> */
+#define LOFT_WGRAD_FORM_RING_GENERIC 5    /* conv_wgrad_ring_kernel<0>: per-row decode */
+#define LOFT_WGRAD_FORM_RING_DENSE 6      /* conv_wgrad_ring_kernel<1>: one tap at offset zero, maps of one size */
+#define LOFT_WGRAD_FORM_RING_SAME 7       /* conv_wgrad_ring_kernel<2>: unit strides, maps of one size, OW >= 32 */
+#define LOFT_WGRAD_FORM_STREAM_GENERIC 8  /* conv_wgrad_stream_kernel<0> */
+#define LOFT_WGRAD_FORM_STREAM_PM_INC 9   /* conv_wgrad_stream_kernel<1>: valid rows, incremental addressing */
+#define LOFT_WGRAD_FORM_STREAM_DENSE 10   /* conv_wgrad_stream_kernel<2> */
+#define LOFT_WGRAD_FORM_STREAM_SAME 11    /* conv_wgrad_stream_kernel<3>: OW >= 64 */
+#define LOFT_WGRAD_FORM_STREAM_PM 12      /* conv_wgrad_stream_kernel<4>: valid rows, per-row decode */
+#define LOFT_WGRAD_FORM_NARROW_GENERIC 13 /* conv_wgrad64_kernel<0> */
+#define LOFT_WGRAD_FORM_NARROW_DENSE 14   /* conv_wgrad64_kernel<1> */
+#define LOFT_WGRAD_FORM_NARROW_SAME 15    /* conv_wgrad64_kernel<2>: OW >= 64 */
+int loft_conv_wgrad_form(int B, int GH, int GW, int Cout, int XH, int XW, int Cin, int OH, int OW, int gos, int ss, int T,
+                         const int* goy, const int* gox, const int* dy, const int* dx, const int* wt, int groups, int splits,
+                         int variant);
 int loft_conv_wgrad_bf16_slots(const void* g, const void* x, float* dw_slots, const void* zero_page, int B, int GH, int GW,
                                int Cout, int XH, int XW, int Cin, int OH, int OW, int gos, int ss, int T, const int* goy_host,
                                const int* gox_host, const int* dy_host, const int* dx_host, const int* wt_host, int groups,
