@@ -299,13 +299,12 @@ def nms_segmented(boxes_sorted, seg_offsets, iou_thr, seg_shift=None, max_segmen
     ws = torch.empty(lib.loft_nms_workspace_bytes(T, max_segment, S), dtype=torch.uint8, device=boxes_sorted.device)
     if img_max is not None:     # segments = (image, level), shift = level * (img_max[image] + 1) computed on the device
         L.dev_check(img_max)
-        L.check(lib.loft_nms_segmented_levels(L.ptr(boxes_sorted), L.ptr(seg_offsets), L.ptr(img_max), int(levels), S, c_int64(T),
-                                              c_int64(max_segment), c_float(iou_thr), c_int(NMS_PREDICATES[predicate]), L.ptr(ws),
+        L.check(lib.loft_nms_segmented_levels(L.ptr(boxes_sorted), L.ptr(seg_offsets), L.ptr(img_max), int(levels), S, T,
+                                              max_segment, iou_thr, NMS_PREDICATES[predicate], L.ptr(ws),
                                               L.ptr(keep), L.stream()), 'loft_nms_segmented_levels')
         return keep
-    L.check(lib.loft_nms_segmented_pred(L.ptr(boxes_sorted), L.ptr(seg_offsets), L.ptr(seg_shift), S, c_int64(T),
-                                        c_int64(max_segment), c_float(iou_thr), c_int(NMS_PREDICATES[predicate]), L.ptr(ws),
-                                        L.ptr(keep), L.stream()), 'loft_nms_segmented_pred')
+    L.check(lib.loft_nms_segmented_pred(L.ptr(boxes_sorted), L.ptr(seg_offsets), L.ptr(seg_shift), S, T, max_segment, iou_thr,
+                                        NMS_PREDICATES[predicate], L.ptr(ws), L.ptr(keep), L.stream()), 'loft_nms_segmented_pred')
     return keep
 
 
@@ -323,11 +322,11 @@ def segmented_sort_desc(keys, seg_offsets, values=None):
     if n == 0:
         return ko, vo
     nbytes = c_int64(0)
-    L.check(lib.loft_segmented_sort_desc(L.ptr(keys), L.ptr(ko), L.ptr(values), L.ptr(vo), c_int64(n), S,
-                                         L.ptr(seg_offsets), c_void_p(0), ctypes.byref(nbytes), L.stream()),
+    L.check(lib.loft_segmented_sort_desc(L.ptr(keys), L.ptr(ko), L.ptr(values), L.ptr(vo), n, S,
+                                         L.ptr(seg_offsets), None, ctypes.byref(nbytes), L.stream()),
             'loft_segmented_sort_desc(query)')
     ws = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device=keys.device)
-    L.check(lib.loft_segmented_sort_desc(L.ptr(keys), L.ptr(ko), L.ptr(values), L.ptr(vo), c_int64(n), S,
+    L.check(lib.loft_segmented_sort_desc(L.ptr(keys), L.ptr(ko), L.ptr(values), L.ptr(vo), n, S,
                                          L.ptr(seg_offsets), L.ptr(ws), ctypes.byref(nbytes), L.stream()),
             'loft_segmented_sort_desc')
     return ko, vo
@@ -407,15 +406,15 @@ def segmented_topk_desc(keys, seg_offsets, k, values=None, max_segment=None, seg
             return segmented_sort_desc(keys, seg_offsets, values)
         ck = torch.empty(tabs['n_cand'], dtype=torch.float32, device=keys.device)
         cv = torch.empty(tabs['n_cand'], dtype=torch.int32, device=keys.device)
-        L.check(lib.loft_segmented_topk_desc(L.ptr(keys), L.ptr(ck), c_void_p(0), L.ptr(cv), tabs['n_run'], L.ptr(tabs['sub_off']), int(k),
-                                             L.ptr(tabs['run_off']), c_void_p(0), L.stream()), 'loft_segmented_topk_desc(stage 1)')
+        L.check(lib.loft_segmented_topk_desc(L.ptr(keys), L.ptr(ck), None, L.ptr(cv), tabs['n_run'], L.ptr(tabs['sub_off']), int(k),
+                                             L.ptr(tabs['run_off']), None, L.stream()), 'loft_segmented_topk_desc(stage 1)')
         L.check(lib.loft_topk_merge_runs(L.ptr(ck), L.ptr(cv), tabs['n_run'], tabs['max_run'], L.ptr(tabs['run_off']),
                                          L.ptr(tabs['run_first']), L.ptr(tabs['run_count']), L.ptr(tabs['run_out']), int(k), L.ptr(ko),
                                          L.ptr(vo), L.stream()), 'loft_topk_merge_runs')
         return ko, vo
     if values is not None:
         values = values.to(torch.int32).contiguous()
-    L.check(lib.loft_segmented_topk_desc(L.ptr(keys), L.ptr(ko), L.ptr(values), L.ptr(vo), S, L.ptr(seg_offsets), int(k), c_void_p(0),
+    L.check(lib.loft_segmented_topk_desc(L.ptr(keys), L.ptr(ko), L.ptr(values), L.ptr(vo), S, L.ptr(seg_offsets), int(k), None,
                                          L.ptr(key_mask), L.stream()), 'loft_segmented_topk_desc')
     return ko, vo
 
@@ -528,7 +527,7 @@ _SLOT_POOLS = {}      # raw stream -> [buffer, words used]: pre-zeroed (absmax, 
 def _amax_slot(device):
     """Two zeroed words for loft_absmax_split_planes_f32, from a pool filled ON THE CURRENT STREAM (the zero fill is ordered
     before every kernel that uses a slot only on the stream that issued it)."""
-    key = (str(device), L.stream().value)
+    key = (str(device), L.stream())
     sp = _SLOT_POOLS.get(key)
     if sp is None or sp[1] + 2 > sp[0].numel():
         sp = _SLOT_POOLS[key] = [torch.zeros(4096, dtype=torch.float32, device=device), 0]
@@ -570,14 +569,14 @@ def split_planes(x, dtype16):
     n = x.numel()
     planes = torch.empty((lib.loft_planes_per_tensor(), n), dtype=dtype16, device=x.device)
     if dtype16 != torch.float16:
-        L.check(lib.loft_split_planes_f32(L.ptr(x), c_int64(n), L.ptr(planes), c_void_p(0), L.stream()), 'loft_split_planes_f32')
+        L.check(lib.loft_split_planes_f32(L.ptr(x), n, L.ptr(planes), None, L.stream()), 'loft_split_planes_f32')
         return planes, None
     amax = _known_amax(x)
     if amax is not None:
-        L.check(lib.loft_split_planes_f32(L.ptr(x), c_int64(n), L.ptr(planes), L.ptr(amax), L.stream()), 'loft_split_planes_f32')
+        L.check(lib.loft_split_planes_f32(L.ptr(x), n, L.ptr(planes), L.ptr(amax), L.stream()), 'loft_split_planes_f32')
         return planes, amax
     amax = _amax_slot(x.device)
-    L.check(lib.loft_absmax_split_planes_f32(L.ptr(x), c_int64(n), L.ptr(planes), L.ptr(amax), L.stream()), 'loft_absmax_split_planes_f32')
+    L.check(lib.loft_absmax_split_planes_f32(L.ptr(x), n, L.ptr(planes), L.ptr(amax), L.stream()), 'loft_absmax_split_planes_f32')
     return planes, amax
 
 
@@ -622,12 +621,12 @@ class _PlanesEntry:
     def __init__(self, val, keep=None):
         self.val = val
         self.keep = keep
-        self.stream = L.stream().value
+        self.stream = L.stream()
         self.event = torch.cuda.Event()
         self.event.record()
 
     def get(self):
-        if L.stream().value != self.stream:
+        if L.stream() != self.stream:
             cur = torch.cuda.current_stream()
             cur.wait_event(self.event)
             for t in self.val:
@@ -699,10 +698,9 @@ def conv_tap(src, wgt, out, B, IH, IW, Cin, Cout, OH, OW, OHf, OWf, taps, ss=1, 
                 e = plib.loft_conv_tap_planes(L.ptr(xp), L.ptr(wp), L.ptr(bias), L.ptr(residual), L.ptr(mask), L.ptr(out),
                                               L.ptr(zero_page(src.device)), B, IH, IW, Cin, Cout, OH, OW, OHf, OWf, os, oo[0], oo[1], ss, T,
                                               L.arr(c_int, [t[0] for t in taps]), L.arr(c_int, [t[1] for t in taps]),
-                                              L.arr(c_int, [t[2] for t in taps]), int(relu), groups, c_int64(src_gs), c_int64(wgt_gs),
-                                              c_int64(out_gs), c_int64(bias_gs), len(terms), L.arr(c_int, [t[0] for t in terms]),
-                                              L.arr(c_int, [t[1] for t in terms]), c_int64(src.numel()), c_int64(wgt.numel()),
-                                              L.ptr(ax), L.ptr(aw), L.ptr(oslot), L.stream())
+                                              L.arr(c_int, [t[2] for t in taps]), int(relu), groups, src_gs, wgt_gs, out_gs, bias_gs,
+                                              len(terms), L.arr(c_int, [t[0] for t in terms]), L.arr(c_int, [t[1] for t in terms]),
+                                              src.numel(), wgt.numel(), L.ptr(ax), L.ptr(aw), L.ptr(oslot), L.stream())
                 if e == 0:
                     PLANES_STATS['planes'] += 1
                     if oslot is not None:
@@ -713,11 +711,10 @@ def conv_tap(src, wgt, out, B, IH, IW, Cin, Cout, OH, OW, OHf, OWf, taps, ss=1, 
         PLANES_STATS['fallback'] += 1
         _drop_amax(out)
         L.check(lib.loft_conv_tap_f32_v(L.ptr(src), L.ptr(wgt), L.ptr(bias), L.ptr(residual), L.ptr(mask), L.ptr(out),
-                                        L.ptr(zero_page(src.device)), B, IH, IW, Cin, Cout, OH, OW, OHf, OWf, os, oo[0],
-                                        oo[1], ss, T, L.arr(c_int, [t[0] for t in taps]), L.arr(c_int, [t[1] for t in taps]),
-                                        L.arr(c_int, [t[2] for t in taps]), int(relu), int(accumulate), groups,
-                                        c_int64(src_gs), c_int64(wgt_gs), c_int64(out_gs), c_int64(bias_gs), _f32_kernel_code(),
-                                        L.stream()), 'loft_conv_tap_f32_v')
+                                        L.ptr(zero_page(src.device)), B, IH, IW, Cin, Cout, OH, OW, OHf, OWf, os, oo[0], oo[1], ss, T,
+                                        L.arr(c_int, [t[0] for t in taps]), L.arr(c_int, [t[1] for t in taps]),
+                                        L.arr(c_int, [t[2] for t in taps]), int(relu), int(accumulate), groups, src_gs, wgt_gs, out_gs,
+                                        bias_gs, _f32_kernel_code(), L.stream()), 'loft_conv_tap_f32_v')
         return out
     _bf16(src), _bf16(wgt)
     if residual is not None:
@@ -749,9 +746,8 @@ def conv_tap(src, wgt, out, B, IH, IW, Cin, Cout, OH, OW, OHf, OWf, taps, ss=1, 
             if e != 1:          # (hipErrorInvalidValue: a launch the head epilogue does not serve -> plain launch, head by the caller)
                 L.check(e, 'loft_conv_tap_bf16_head')
     L.check(lib.loft_conv_tap_bf16_v(L.ptr(src), L.ptr(wgt), L.ptr(bias), L.ptr(residual), L.ptr(mask), L.ptr(out),
-                                     L.ptr(zero_page(src.device)), B, IH, IW, Cin, Cout, OH, OW, OHf, OWf, os, oo[0],
-                                     oo[1], ss, T, dy, dx, wt, int(relu), int(out_f32), int(accumulate), groups,
-                                     c_int64(src_gs), c_int64(wgt_gs), c_int64(out_gs), c_int64(bias_gs), int(variant),
+                                     L.ptr(zero_page(src.device)), B, IH, IW, Cin, Cout, OH, OW, OHf, OWf, os, oo[0], oo[1], ss, T, dy, dx,
+                                     wt, int(relu), int(out_f32), int(accumulate), groups, src_gs, wgt_gs, out_gs, bias_gs, int(variant),
                                      L.stream()), 'loft_conv_tap_bf16_v')
     _prof_end(_ev, 'conv_tap', 2.0 * groups * B * OH * OW * Cout * Cin * T, (groups, B, OH, OW, Cin, Cout, T, ss, os))
     return out
@@ -865,7 +861,7 @@ def pack_k8(mats, outs=None, desc=None):
             if m.shape[-1] % 8 or not m.is_contiguous() or m.numel() != m.shape[-1] * m.shape[-2] or m.dtype != L.act16():
                 raise L.LoftHipError(f'pack_k8: {tuple(m.shape)} {m.dtype}')
         desc = h2d([[m.data_ptr(), o.data_ptr(), m.shape[-2], m.shape[-1]] for m, o in zip(mats, outs)], torch.int64, mats[0].device)
-    L.check(lib.loft_pack_k8_multi(L.ptr(desc), len(mats), c_int64(max(m.numel() // 8 for m in mats)), L.stream()), 'loft_pack_k8_multi')
+    L.check(lib.loft_pack_k8_multi(L.ptr(desc), len(mats), max(m.numel() // 8 for m in mats), L.stream()), 'loft_pack_k8_multi')
     return outs, desc
 
 
@@ -893,8 +889,8 @@ def bneck_pair(a_in, w1k8, bias1, res, w2k8, bias2, mask1=None, mask2=None, vari
     mid = empty_nhwc(B, C, H, W, L.act16(), a_in.device)
     out2 = empty_nhwc(B, P, H, W, L.act16(), a_in.device)
     L.check(lib.loft_bneck_pair_bf16_v(L.ptr(a_in), L.ptr(w1k8), L.ptr(bias1), L.ptr(res), L.ptr(mask1), L.ptr(mid), L.ptr(w2k8),
-                                       L.ptr(bias2), L.ptr(mask2), L.ptr(out2), c_int64(B * H * W), P, C, int(variant), L.stream()),
-            'loft_bneck_pair_bf16')
+                                       L.ptr(bias2), L.ptr(mask2), L.ptr(out2), B * H * W, P, C, int(variant), L.stream()),
+            'loft_bneck_pair_bf16_v')
     return mid, out2
 
 
@@ -982,12 +978,11 @@ def conv_wgrad(g, x, B, GH, GW, Cout, XH, XW, Cin, OH, OW, taps, n_wtaps, gos=1,
             # db is the plain [groups, Cout] accumulator and the caller named a tap whose G rows are complete
             db_fused = (PLANES_DB_FUSED and db is not None and db_tap != -1 and tuple(db.shape) == (groups, Cout) and db.is_contiguous()
                         and db.dtype == torch.float32)
-            e = plib.loft_conv_wgrad_planes(L.ptr(gp), L.ptr(xp), L.ptr(dw), L.ptr(zero_page(g.device)), B, GH, GW, Cout, XH, XW, Cin,
-                                            OH, OW, gos, ss, len(taps), A(0), A(1), A(2), A(3), A(4), groups, c_int64(g_gs),
-                                            c_int64(x_gs), c_int64(n_wtaps * Cout * Cin), len(terms),
-                                            L.arr(c_int, [t[1] for t in terms]), L.arr(c_int, [t[0] for t in terms]),
-                                            c_int64(g.numel()), c_int64(x.numel()), L.ptr(ag), L.ptr(ax),
-                                            L.ptr(db) if db_fused else c_void_p(0), int(db_tap) if db_fused else -1, L.stream())
+            e = plib.loft_conv_wgrad_planes(L.ptr(gp), L.ptr(xp), L.ptr(dw), L.ptr(zero_page(g.device)), B, GH, GW, Cout, XH, XW, Cin, OH,
+                                            OW, gos, ss, len(taps), A(0), A(1), A(2), A(3), A(4), groups, g_gs, x_gs, n_wtaps * Cout * Cin,
+                                            len(terms), L.arr(c_int, [t[1] for t in terms]), L.arr(c_int, [t[0] for t in terms]), g.numel(),
+                                            x.numel(), L.ptr(ag), L.ptr(ax), L.ptr(db) if db_fused else None,
+                                            int(db_tap) if db_fused else -1, L.stream())
             if e == 0:
                 PLANES_STATS['planes'] += 1
                 done = True
@@ -999,12 +994,12 @@ def conv_wgrad(g, x, B, GH, GW, Cout, XH, XW, Cin, OH, OW, taps, n_wtaps, gos=1,
         if not done:
             PLANES_STATS['fallback'] += 1
             L.check(lib.loft_conv_wgrad_f32_v(L.ptr(g), L.ptr(x), L.ptr(dw), B, GH, GW, Cout, XH, XW, Cin, OH, OW, gos, ss, len(taps),
-                                          A(0), A(1), A(2), A(3), A(4), groups, c_int64(g_gs), c_int64(x_gs),
-                                              c_int64(n_wtaps * Cout * Cin), _f32_kernel_code(), L.stream()), 'loft_conv_wgrad_f32_v')
+                                          A(0), A(1), A(2), A(3), A(4), groups, g_gs, x_gs,
+                                              n_wtaps * Cout * Cin, _f32_kernel_code(), L.stream()), 'loft_conv_wgrad_f32_v')
         if db is not None:
             if _dense(g) and g.dim() == 4 and Cout % 4 == 0 and g.is_contiguous(memory_format=torch.channels_last):
                 tmp = db if (db.shape[1] == Cout and db.is_contiguous()) else torch.zeros(groups, Cout, dtype=torch.float32, device=g.device)
-                L.check(lib.loft_colsum_f32(L.ptr(g), c_int64(B * GH * GW), Cout, groups, L.ptr(tmp), L.stream()), 'loft_colsum_f32')
+                L.check(lib.loft_colsum_f32(L.ptr(g), B * GH * GW, Cout, groups, L.ptr(tmp), L.stream()), 'loft_colsum_f32')
                 if tmp is not db:
                     db += tmp[:, :db.shape[1]]
             else:
@@ -1021,8 +1016,8 @@ def conv_wgrad(g, x, B, GH, GW, Cout, XH, XW, Cin, OH, OW, taps, n_wtaps, gos=1,
         ws = torch.empty(lib.loft_conv_wgrad_patch_workspace_bytes(B, OH, OW, Cout, Cin, len(taps), groups), dtype=torch.uint8,
                          device=g.device)
         L.check(lib.loft_conv_wgrad_patch_bf16(L.ptr(g), L.ptr(x), L.ptr(dw), L.ptr(zero_page(g.device)), B, OH, OW, Cout, Cin,
-                                               len(taps), A(2), A(3), A(4), groups, c_int64(g_gs), c_int64(x_gs),
-                                               c_int64(n_wtaps * Cout * Cin), L.ptr(db), L.ptr(ws), L.stream()),
+                                               len(taps), A(2), A(3), A(4), groups, g_gs, x_gs,
+                                               n_wtaps * Cout * Cin, L.ptr(db), L.ptr(ws), L.stream()),
                 'loft_conv_wgrad_patch_bf16')
         _prof_end(_ev, 'conv_wgrad', 2.0 * groups * B * OH * OW * Cout * Cin * len(taps), (groups, B, OH, OW, Cin, Cout, len(taps), ss, gos))
         return dw
@@ -1036,7 +1031,7 @@ def conv_wgrad(g, x, B, GH, GW, Cout, XH, XW, Cin, OH, OW, taps, n_wtaps, gos=1,
             dw = pooled_scratch((groups, S, n_wtaps, Cout, Cin), g.device)
             L.check(lib.loft_conv_wgrad_bf16_slots(L.ptr(g), L.ptr(x), L.ptr(dw), L.ptr(zero_page(g.device)), B, GH, GW, Cout, XH,
                                                    XW, Cin, OH, OW, gos, ss, len(taps), A(0), A(1), A(2), A(3), A(4), groups,
-                                                   c_int64(g_gs), c_int64(x_gs), S, splits, L.ptr(db), int(db_tap),
+                                                   g_gs, x_gs, S, splits, L.ptr(db), int(db_tap),
                                                    int(_wgrad_variant(groups, B, OH, OW, Cin, Cout, len(taps), ss, gos)), L.stream()), 'loft_conv_wgrad_bf16_slots')
             _prof_end(_ev, 'conv_wgrad', 2.0 * groups * B * OH * OW * Cout * Cin * len(taps), (groups, B, OH, OW, Cin, Cout, len(taps), ss, gos))
             return dw
@@ -1044,7 +1039,7 @@ def conv_wgrad(g, x, B, GH, GW, Cout, XH, XW, Cin, OH, OW, taps, n_wtaps, gos=1,
         dw = pooled_zeros((groups, n_wtaps, Cout, Cin), g.device)
     L.check(lib.loft_conv_wgrad_bf16_v(L.ptr(g), L.ptr(x), L.ptr(dw), L.ptr(zero_page(g.device)), B, GH, GW, Cout, XH,
                                        XW, Cin, OH, OW, gos, ss, len(taps), A(0), A(1), A(2), A(3), A(4), groups,
-                                       c_int64(g_gs), c_int64(x_gs), c_int64(n_wtaps * Cout * Cin), splits, L.ptr(db),
+                                       g_gs, x_gs, n_wtaps * Cout * Cin, splits, L.ptr(db),
                                        int(db_tap), int(_wgrad_variant(groups, B, OH, OW, Cin, Cout, len(taps), ss, gos)), L.stream()),
             'loft_conv_wgrad_bf16_v')
     _prof_end(_ev, 'conv_wgrad', 2.0 * groups * B * OH * OW * Cout * Cin * len(taps), (groups, B, OH, OW, Cin, Cout, len(taps), ss, gos))
@@ -1101,12 +1096,11 @@ def relu_bwd(g, y):
     if g.dtype == torch.float32 and y.dtype == torch.float32:          # fp32 parity mode
         # (the masked gradient is split into operand planes next: the kernel leaves its absmax with it -- kernels._known_amax)
         slot = _amax_slot(g.device) if (AMAX_FROM_PRODUCER and F32_CONTRACT in (F32_PLANES_F16, F32_PLANES_F16X4)) else None
-        L.check(lib.loft_relu_bwd_f32(L.ptr(g), L.ptr(y), L.ptr(out), c_int64(g.numel()), L.ptr(slot), L.stream()), 'loft_relu_bwd_f32')
+        L.check(lib.loft_relu_bwd_f32(L.ptr(g), L.ptr(y), L.ptr(out), g.numel(), L.ptr(slot), L.stream()), 'loft_relu_bwd_f32')
         if slot is not None:
             out._loft_amax = (slot, out.data_ptr(), out._version, out.numel())
         return out
-    L.check(lib.loft_relu_bwd_bf16(L.ptr(_bf16(g)), L.ptr(_bf16(y)), L.ptr(out), c_int64(g.numel()), L.stream()),
-            'loft_relu_bwd_bf16')
+    L.check(lib.loft_relu_bwd_bf16(L.ptr(_bf16(g)), L.ptr(_bf16(y)), L.ptr(out), g.numel(), L.stream()), 'loft_relu_bwd_bf16')
     return out
 
 
@@ -1115,8 +1109,7 @@ def colsum(x2d_like, C):
     lib = L.load()
     L.dev_check(x2d_like)
     out = torch.zeros(C, dtype=torch.float32, device=x2d_like.device)
-    L.check(lib.loft_colsum_bf16(L.ptr(_bf16(x2d_like)), c_int64(x2d_like.numel() // C), C, L.ptr(out), L.stream()),
-            'loft_colsum_bf16')
+    L.check(lib.loft_colsum_bf16(L.ptr(_bf16(x2d_like)), x2d_like.numel() // C, C, L.ptr(out), L.stream()), 'loft_colsum_bf16')
     return out
 
 
@@ -1259,8 +1252,7 @@ def cast_bf16(x_f32):
     lib = L.load()
     L.dev_check(x_f32)
     out = torch.empty_like(x_f32, dtype=L.act16())
-    L.check(lib.loft_cast_f32_to_bf16(L.ptr(x_f32), L.ptr(out), c_int64(x_f32.numel()), L.stream()),
-            'loft_cast_f32_to_bf16')
+    L.check(lib.loft_cast_f32_to_bf16(L.ptr(x_f32), L.ptr(out), x_f32.numel(), L.stream()), 'loft_cast_f32_to_bf16')
     return out
 
 
@@ -1268,23 +1260,21 @@ def add_bf16(a, b):
     lib = L.load()
     L.dev_check(a, b)
     out = torch.empty_like(a)
-    L.check(lib.loft_add_bf16(L.ptr(_bf16(a)), L.ptr(_bf16(b)), L.ptr(out), c_int64(a.numel()), L.stream()),
-            'loft_add_bf16')
+    L.check(lib.loft_add_bf16(L.ptr(_bf16(a)), L.ptr(_bf16(b)), L.ptr(out), a.numel(), L.stream()), 'loft_add_bf16')
     return out
 
 
 def sumsq_(g_flat, out):
     lib = L.load()
-    L.check(lib.loft_sumsq_f32(L.ptr(g_flat), c_int64(g_flat.numel()), L.ptr(out), L.stream()), 'loft_sumsq_f32')
+    L.check(lib.loft_sumsq_f32(L.ptr(g_flat), g_flat.numel(), L.ptr(out), L.stream()), 'loft_sumsq_f32')
     return out
 
 
 def sgd_momentum_(p, g, m, gnorm_sq, max_norm, lr, momentum, weight_decay, grad_scale=1.0):
     lib = L.load()
     L.dev_check(p, g, m, gnorm_sq)
-    L.check(lib.loft_sgd_momentum_f32(L.ptr(p), L.ptr(g), L.ptr(m), c_int64(p.numel()), L.ptr(gnorm_sq),
-                                      c_float(max_norm), c_float(lr), c_float(momentum), c_float(weight_decay),
-                                      c_float(grad_scale), L.stream()), 'loft_sgd_momentum_f32')
+    L.check(lib.loft_sgd_momentum_f32(L.ptr(p), L.ptr(g), L.ptr(m), p.numel(), L.ptr(gnorm_sq), max_norm, lr, momentum, weight_decay,
+                                      grad_scale, L.stream()), 'loft_sgd_momentum_f32')
 
 
 # ---- dynamic loss scaling: the device-side state of include/loft_hip.h (LOFT_LS_*), held as a float32 tensor of LS_WORDS words
@@ -1319,9 +1309,8 @@ def sgd_momentum_scaled_(p, g, m, gnorm_sq, max_norm, lr, momentum, weight_decay
     lib = L.load()
     L.dev_check(p, g, m, gnorm_sq, state)
     _ls_state_check(state)
-    L.check(lib.loft_sgd_momentum_scaled_f32(L.ptr(p), L.ptr(g), L.ptr(m), c_int64(p.numel()), L.ptr(gnorm_sq),
-                                             c_float(max_norm), c_float(lr), c_float(momentum), c_float(weight_decay),
-                                             c_float(inv_world), L.ptr(state), L.stream()), 'loft_sgd_momentum_scaled_f32')
+    L.check(lib.loft_sgd_momentum_scaled_f32(L.ptr(p), L.ptr(g), L.ptr(m), p.numel(), L.ptr(gnorm_sq), max_norm, lr, momentum, weight_decay,
+                                             inv_world, L.ptr(state), L.stream()), 'loft_sgd_momentum_scaled_f32')
 
 
 def loss_scale_update_(state, gnorm_sq, inv_world, growth_factor, backoff_factor, growth_interval, min_scale, max_scale):
@@ -1329,9 +1318,8 @@ def loss_scale_update_(state, gnorm_sq, inv_world, growth_factor, backoff_factor
     lib = L.load()
     L.dev_check(state, gnorm_sq)
     _ls_state_check(state)
-    L.check(lib.loft_loss_scale_update(L.ptr(state), L.ptr(gnorm_sq), c_float(inv_world), c_float(growth_factor),
-                                       c_float(backoff_factor), c_int(int(growth_interval)), c_float(min_scale),
-                                       c_float(max_scale), L.stream()), 'loft_loss_scale_update')
+    L.check(lib.loft_loss_scale_update(L.ptr(state), L.ptr(gnorm_sq), inv_world, growth_factor, backoff_factor, int(growth_interval),
+                                       min_scale, max_scale, L.stream()), 'loft_loss_scale_update')
 
 
 # ------------------------------------------------------------------ boxes / targets
@@ -1349,9 +1337,8 @@ def iou_assign(boxes, nbox, gts, ngt, pos_thr, neg_thr, min_pos, low_quality=Tru
     gtmax = torch.empty(B, max(K, 1), dtype=torch.int32, device=dev)
     gt_inds = torch.empty(B, N, dtype=torch.int64, device=dev)
     nbox_i, ngt_i = nbox.int().contiguous(), ngt.int().contiguous()  # keep alive across the launch
-    L.check(lib.loft_iou_assign(L.ptr(boxes), L.ptr(nbox_i), N, L.ptr(gts), L.ptr(ngt_i), K, B,
-                                c_float(pos_thr), c_float(neg_thr), c_float(min_pos), int(low_quality), L.ptr(max_ov),
-                                L.ptr(argmax), L.ptr(gtmax), L.ptr(gt_inds), L.stream()), 'loft_iou_assign')
+    L.check(lib.loft_iou_assign(L.ptr(boxes), L.ptr(nbox_i), N, L.ptr(gts), L.ptr(ngt_i), K, B, pos_thr, neg_thr, min_pos, int(low_quality),
+                                L.ptr(max_ov), L.ptr(argmax), L.ptr(gtmax), L.ptr(gt_inds), L.stream()), 'loft_iou_assign')
     return gt_inds, max_ov
 
 
@@ -1361,9 +1348,8 @@ def delta2bbox(rois, deltas, means, stds, max_shape=None, wh_ratio_clip=16 / 100
     rois, deltas = rois.float().contiguous(), deltas.float().contiguous()
     out = torch.empty_like(rois)
     mh, mw = (float(max_shape[0]), float(max_shape[1])) if max_shape is not None else (0.0, 0.0)
-    L.check(lib.loft_delta2bbox(L.ptr(rois), L.ptr(deltas), c_int64(rois.shape[0]), L.arr(c_float, list(means)),
-                                L.arr(c_float, list(stds)), c_float(wh_ratio_clip), c_float(mh), c_float(mw), L.ptr(out),
-                                L.stream()), 'loft_delta2bbox')
+    L.check(lib.loft_delta2bbox(L.ptr(rois), L.ptr(deltas), rois.shape[0], L.arr(c_float, list(means)), L.arr(c_float, list(stds)),
+                                wh_ratio_clip, mh, mw, L.ptr(out), L.stream()), 'loft_delta2bbox')
     return out
 
 
@@ -1372,7 +1358,7 @@ def bbox2delta(proposals, gt, means, stds):
     L.dev_check(proposals, gt)
     proposals, gt = proposals.float().contiguous(), gt.float().contiguous()
     out = torch.empty_like(proposals)
-    L.check(lib.loft_bbox2delta(L.ptr(proposals), L.ptr(gt), c_int64(proposals.shape[0]), L.arr(c_float, list(means)),
+    L.check(lib.loft_bbox2delta(L.ptr(proposals), L.ptr(gt), proposals.shape[0], L.arr(c_float, list(means)),
                                 L.arr(c_float, list(stds)), L.ptr(out), L.stream()), 'loft_bbox2delta')
     return out
 
@@ -1381,8 +1367,7 @@ def rpn_scores(head, A, img_stride, lvl_off, keys):
     lib = L.load()
     head = _nhwc(head)
     B, Cp, H, W = head.shape
-    L.check(lib.loft_rpn_scores(L.ptr(head), B, H, W, Cp, A, c_int64(img_stride), c_int64(lvl_off), L.ptr(keys),
-                                L.stream()), 'loft_rpn_scores')
+    L.check(lib.loft_rpn_scores(L.ptr(head), B, H, W, Cp, A, img_stride, lvl_off, L.ptr(keys), L.stream()), 'loft_rpn_scores')
 
 
 def rpn_decode(head, sorted_idx, A, img_stride, lvl_off, topk, base_anchors, stride, means, stds, max_shape, cand_stride,
@@ -1390,11 +1375,9 @@ def rpn_decode(head, sorted_idx, A, img_stride, lvl_off, topk, base_anchors, str
     lib = L.load()
     head = _nhwc(head)
     B, Cp, H, W = head.shape
-    L.check(lib.loft_rpn_decode(L.ptr(head), L.ptr(sorted_idx), B, H, W, Cp, A, c_int64(img_stride), c_int64(lvl_off),
-                                int(topk), L.ptr(base_anchors), int(stride), L.arr(c_float, list(means)),
-                                L.arr(c_float, list(stds)), c_float(wh_ratio_clip), c_float(max_shape[0]),
-                                c_float(max_shape[1]), c_int64(cand_stride), c_int64(cand_off), L.ptr(out_boxes),
-                                L.stream()), 'loft_rpn_decode')
+    L.check(lib.loft_rpn_decode(L.ptr(head), L.ptr(sorted_idx), B, H, W, Cp, A, img_stride, lvl_off, int(topk), L.ptr(base_anchors),
+                                int(stride), L.arr(c_float, list(means)), L.arr(c_float, list(stds)), wh_ratio_clip, max_shape[0],
+                                max_shape[1], cand_stride, cand_off, L.ptr(out_boxes), L.stream()), 'loft_rpn_decode')
 
 
 def rpn_scores_levels(heads, A, img_stride, lvl_offs, keys, img_max=None):
@@ -1405,7 +1388,7 @@ def rpn_scores_levels(heads, A, img_stride, lvl_offs, keys, img_max=None):
     n = len(heads)
     L.check(lib.loft_rpn_scores_levels(L.arr(c_void_p, [h.data_ptr() for h in heads]), L.arr(c_int, [int(h.shape[2]) for h in heads]),
                                        L.arr(c_int, [int(h.shape[3]) for h in heads]), L.arr(c_int64, [int(o) for o in lvl_offs[:n]]),
-                                       n, B, Cp, A, c_int64(img_stride), L.ptr(keys), L.ptr(img_max), L.stream()),
+                                       n, B, Cp, A, img_stride, L.ptr(keys), L.ptr(img_max), L.stream()),
             'loft_rpn_scores_levels')
     return heads
 
@@ -1421,9 +1404,9 @@ def rpn_decode_levels(heads, sorted_idx, sorted_keys, A, img_stride, lvl_offs, t
                                        L.arr(c_int, [int(h.shape[2]) for h in heads]), L.arr(c_int, [int(h.shape[3]) for h in heads]),
                                        L.arr(c_int, [int(t) for t in topk]), L.arr(c_int, [int(s) for s in strides]),
                                        L.arr(c_int64, [int(o) for o in lvl_offs[:n]]), L.arr(c_int64, [int(o) for o in cand_offs[:n]]), n,
-                                       L.ptr(sorted_idx), L.ptr(sorted_keys), B, Cp, A, c_int64(img_stride),
-                                       L.arr(c_float, list(means)), L.arr(c_float, list(stds)), c_float(wh_ratio_clip),
-                                       c_float(max_shape[0]), c_float(max_shape[1]), c_int64(cand_stride), L.ptr(out_boxes),
+                                       L.ptr(sorted_idx), L.ptr(sorted_keys), B, Cp, A, img_stride,
+                                       L.arr(c_float, list(means)), L.arr(c_float, list(stds)), wh_ratio_clip,
+                                       max_shape[0], max_shape[1], cand_stride, L.ptr(out_boxes),
                                        L.ptr(out_scores), L.ptr(img_max), L.stream()), 'loft_rpn_decode_levels')
 
 
@@ -1433,7 +1416,7 @@ def rpn_finalize(top_scores, top_idx, cand_boxes, B, seg_stride, post):
     L.dev_check(top_scores, top_idx, cand_boxes)
     props = torch.empty(B, post, 5, dtype=torch.float32, device=top_scores.device)
     counts = torch.empty(B, dtype=torch.int64, device=top_scores.device)
-    L.check(lib.loft_rpn_finalize(L.ptr(top_scores), L.ptr(top_idx), L.ptr(cand_boxes), int(B), c_int64(seg_stride), int(post),
+    L.check(lib.loft_rpn_finalize(L.ptr(top_scores), L.ptr(top_idx), L.ptr(cand_boxes), int(B), seg_stride, int(post),
                                   L.ptr(props), L.ptr(counts), L.stream()), 'loft_rpn_finalize')
     return props, counts
 
@@ -1444,8 +1427,7 @@ def foa_targets(pos_boxes, pos_gt_offsets, stds=(0.5, 0.5)):
     pos_boxes, pos_gt_offsets = pos_boxes.float().contiguous(), pos_gt_offsets.float().contiguous()
     n = pos_boxes.shape[0]
     out = torch.empty(4 * n, 2, dtype=torch.float32, device=pos_boxes.device)
-    L.check(lib.loft_foa_targets(L.ptr(pos_boxes), L.ptr(pos_gt_offsets), c_int64(n), c_float(stds[0]), c_float(stds[1]),
-                                 L.ptr(out), L.stream()), 'loft_foa_targets')
+    L.check(lib.loft_foa_targets(L.ptr(pos_boxes), L.ptr(pos_gt_offsets), n, stds[0], stds[1], L.ptr(out), L.stream()), 'loft_foa_targets')
     return out
 
 
@@ -1455,8 +1437,8 @@ def foa_fuse_decode(pred, boxes, stds=(0.5, 0.5), max_shape=(1024, 1024)):
     pred, boxes = pred.float().contiguous(), boxes[:, :4].float().contiguous()
     n = boxes.shape[0]
     out = torch.empty(n, 2, dtype=torch.float32, device=pred.device)
-    L.check(lib.loft_foa_fuse_decode(L.ptr(pred), L.ptr(boxes), c_int64(n), c_float(stds[0]), c_float(stds[1]),
-                                     c_float(max_shape[0]), c_float(max_shape[1]), L.ptr(out), L.stream()),
+    L.check(lib.loft_foa_fuse_decode(L.ptr(pred), L.ptr(boxes), n, stds[0], stds[1],
+                                     max_shape[0], max_shape[1], L.ptr(out), L.stream()),
             'loft_foa_fuse_decode')
     return out
 
@@ -1468,8 +1450,8 @@ def offset_targets(pos_boxes, pos_gt_offsets, means=(0., 0.), stds=(0.5, 0.5), r
     pos_boxes, pos_gt_offsets = pos_boxes.float().contiguous(), pos_gt_offsets.float().contiguous()
     n = pos_boxes.shape[0]
     out = torch.empty(n, reg_num, dtype=torch.float32, device=pos_boxes.device)
-    L.check(lib.loft_offset_targets(L.ptr(pos_boxes), L.ptr(pos_gt_offsets), c_int64(n), c_float(means[0]), c_float(means[1]),
-                                    c_float(stds[0]), c_float(stds[1]), c_int(reg_num), L.ptr(out), L.stream()),
+    L.check(lib.loft_offset_targets(L.ptr(pos_boxes), L.ptr(pos_gt_offsets), n, means[0], means[1],
+                                    stds[0], stds[1], reg_num, L.ptr(out), L.stream()),
             'loft_offset_targets')
     return out
 
@@ -1481,9 +1463,8 @@ def offset_decode(pred, boxes, means=(0., 0.), stds=(0.5, 0.5), max_shape=(1024,
     pred, boxes = pred.float().contiguous(), boxes[:, :4].float().contiguous()
     n, reg_num = boxes.shape[0], int(pred.shape[1])
     out = torch.empty(n, 2, dtype=torch.float32, device=pred.device)
-    L.check(lib.loft_offset_decode(L.ptr(pred), L.ptr(boxes), c_int64(n), c_float(means[0]), c_float(means[1]),
-                                   c_float(stds[0]), c_float(stds[1]), c_float(max_shape[0]), c_float(max_shape[1]),
-                                   c_int(reg_num), c_int(1 if polar else 0), L.ptr(out), L.stream()), 'loft_offset_decode')
+    L.check(lib.loft_offset_decode(L.ptr(pred), L.ptr(boxes), n, means[0], means[1], stds[0], stds[1], max_shape[0], max_shape[1], reg_num,
+                                   1 if polar else 0, L.ptr(out), L.stream()), 'loft_offset_decode')
     return out
 
 
@@ -1557,14 +1538,14 @@ def mask_target(masks_u8, boxes, gt_idx, S=28):
         #  front of the mask branch)
         addr = h2d(np.concatenate([m.data_ptr() + np.arange(m.shape[0], dtype=np.int64) * (H * W) for m in ms])
                    if ms else np.zeros(0, np.int64), torch.int64, boxes.device)
-        L.check(lib.loft_mask_target(None, H, W, L.ptr(boxes), L.ptr(gt_idx), c_int64(n), S, L.ptr(out), L.ptr(addr), L.stream()),
+        L.check(lib.loft_mask_target(None, H, W, L.ptr(boxes), L.ptr(gt_idx), n, S, L.ptr(out), L.ptr(addr), L.stream()),
                 'loft_mask_target')
         out._keep = ms      # the address table points into these tensors
         return out
     L.dev_check(masks_u8, boxes, gt_idx)
     masks_u8 = masks_u8.contiguous()
     L.check(lib.loft_mask_target(L.ptr(masks_u8), masks_u8.shape[1], masks_u8.shape[2], L.ptr(boxes),
-                                 L.ptr(gt_idx), c_int64(n), S, L.ptr(out), None, L.stream()),
+                                 L.ptr(gt_idx), n, S, L.ptr(out), None, L.stream()),
             'loft_mask_target')
     return out
 
@@ -1584,8 +1565,8 @@ def soft_nms(boxes, scores, iou_threshold=0.3, sigma=0.5, min_score=1e-3, method
     ws = torch.empty(lib.loft_soft_nms_workspace_bytes(n), dtype=torch.uint8, device=boxes.device)
     cnt = torch.zeros(1, dtype=torch.int32, device=boxes.device)
     m = {'naive': 0, 'linear': 1, 'gaussian': 2}[method]
-    L.check(lib.loft_soft_nms(L.ptr(boxes), L.ptr(scores), c_int64(n), c_float(iou_threshold), c_float(sigma),
-                              c_float(min_score), m, L.ptr(ws), L.ptr(dets), L.ptr(inds), L.ptr(cnt), L.stream()),
+    L.check(lib.loft_soft_nms(L.ptr(boxes), L.ptr(scores), n, iou_threshold, sigma,
+                              min_score, m, L.ptr(ws), L.ptr(dets), L.ptr(inds), L.ptr(cnt), L.stream()),
             'loft_soft_nms')
     k = int(cnt.item())
     return dets[:k], inds[:k]
@@ -1616,8 +1597,7 @@ def mask_paste(logits, boxes, img_h, img_w, thr=0.5):
     logits, boxes = logits.float().contiguous(), boxes.float().contiguous()
     N, S = logits.shape[0], logits.shape[-1]
     out = torch.empty(N, img_h, img_w, dtype=torch.uint8, device=logits.device)
-    L.check(lib.loft_mask_paste(L.ptr(logits), L.ptr(boxes), N, S, int(img_h), int(img_w), c_float(thr), L.ptr(out),
-                                L.stream()), 'loft_mask_paste')
+    L.check(lib.loft_mask_paste(L.ptr(logits), L.ptr(boxes), N, S, int(img_h), int(img_w), thr, L.ptr(out), L.stream()), 'loft_mask_paste')
     return out
 
 
@@ -1853,7 +1833,7 @@ def fold_pack(w, conv_bias=None, bn=None, eps=1e-5, want_fwd=True, want_dgrad=Tr
     if bn is not None:
         g, b, m, v = [t.contiguous() for t in bn]
     cb = conv_bias.contiguous() if conv_bias is not None else None
-    L.check(lib.loft_fold_pack(L.ptr(w), L.ptr(cb), L.ptr(g), L.ptr(b), L.ptr(m), L.ptr(v), c_float(eps), Cout, Cin, T,
+    L.check(lib.loft_fold_pack(L.ptr(w), L.ptr(cb), L.ptr(g), L.ptr(b), L.ptr(m), L.ptr(v), eps, Cout, Cin, T,
                                L.ptr(wp), L.ptr(wpt), L.ptr(bias), int(dtype == torch.float32), CoutP, CinP, L.stream()),
             'loft_fold_pack')
     return wp, wpt, bias
@@ -1997,17 +1977,17 @@ class PrepackRegistry:
         if zero:
             for grp in groups:
                 grp['slot'].zero_()
-        L.check(plib.loft_fold_f32_multi(L.ptr(fdesc), fn, c_int64(fb), L.stream()), 'loft_fold_f32_multi')
+        L.check(plib.loft_fold_f32_multi(L.ptr(fdesc), fn, fb, L.stream()), 'loft_fold_f32_multi')
         if sn:
-            L.check(plib.loft_split_planes_f32_multi(L.ptr(sdesc), sn, c_int64(sb), L.stream()), 'loft_split_planes_f32_multi')
+            L.check(plib.loft_split_planes_f32_multi(L.ptr(sdesc), sn, sb, L.stream()), 'loft_split_planes_f32_multi')
         return cached
 
     def _run_f32_cached(self, groups):
         plib = L.load_for(torch.float16)
         fdesc, fb, fn, sdesc, sb, sn = self.f32desc
-        L.check(plib.loft_fold_f32_multi(L.ptr(fdesc), fn, c_int64(fb), L.stream()), 'loft_fold_f32_multi')
+        L.check(plib.loft_fold_f32_multi(L.ptr(fdesc), fn, fb, L.stream()), 'loft_fold_f32_multi')
         if sn:
-            L.check(plib.loft_split_planes_f32_multi(L.ptr(sdesc), sn, c_int64(sb), L.stream()), 'loft_split_planes_f32_multi')
+            L.check(plib.loft_split_planes_f32_multi(L.ptr(sdesc), sn, sb, L.stream()), 'loft_split_planes_f32_multi')
 
     def k8(self, m):
         """K8 layout ([K/8, rows, 8]) of the registry packing m ([rows, K] view of a buffer request() returned), valid for the
@@ -2068,7 +2048,7 @@ class PrepackRegistry:
             dev = self.jobs[self.order[0]]['wp'].device
             self.desc = h2d(rows, torch.int64, dev)
             self.nrows = len(rows)
-        L.check(lib.loft_fold_pack_multi(L.ptr(self.desc), self.nrows, c_int64(self.nchunks), L.stream()), 'loft_fold_pack_multi')
+        L.check(lib.loft_fold_pack_multi(L.ptr(self.desc), self.nrows, self.nchunks, L.stream()), 'loft_fold_pack_multi')
         for key in self.order:                # n-major records: the [K][O] operand is the transpose of the [O][K] one
             grp = self.jobs[key]
             if grp['flat'] is not None and grp['wpt'] is not None:
@@ -2156,7 +2136,7 @@ def fused_loss(mode, pred, target, weight=None, avg_factor=None, count=None, sca
             af = af.float()
     elif avg_factor is not None:
         cnt = float(avg_factor)
-    key = (dev.index, L.stream().value)
+    key = (dev.index, L.stream())
     if key not in _LOSS_SCRATCH:             # per stream: the ticket counter must not be shared by concurrent launches
         _LOSS_SCRATCH[key] = torch.zeros(1, dtype=torch.int32, device=dev)
     counter = _LOSS_SCRATCH[key]
@@ -2164,9 +2144,8 @@ def fused_loss(mode, pred, target, weight=None, avg_factor=None, count=None, sca
     grad = torch.empty(pred.shape, dtype=torch.float32, device=dev)
     out = torch.empty(2, dtype=torch.float32, device=dev)
     d1, d2, s0, s1, s2 = view
-    L.check(lib.loft_fused_loss_v2(m, L.ptr(pred), c_int64(d1), c_int64(d2), c_int64(s0), c_int64(s1), c_int64(s2), L.ptr(target),
-                                   1 if (target_ge1 and m == 2) else 0, L.ptr(weight), wkind, c_int64(wdiv), c_int64(n), int(C),
-                                   L.ptr(af), c_float(max(cnt, 1e-30)), c_float(scale), c_float(beta), L.ptr(grad), L.ptr(partial),
+    L.check(lib.loft_fused_loss_v2(m, L.ptr(pred), d1, d2, s0, s1, s2, L.ptr(target), 1 if (target_ge1 and m == 2) else 0, L.ptr(weight),
+                                   wkind, wdiv, n, int(C), L.ptr(af), max(cnt, 1e-30), scale, beta, L.ptr(grad), L.ptr(partial),
                                    L.ptr(counter), L.ptr(out), 1 if (want_acc and m == 3) else 0, L.stream()), 'loft_fused_loss_v2')
     return (out[:1], grad, out[1:]) if want_acc else (out[:1], grad)
 
@@ -2193,7 +2172,7 @@ def rpn_sample_gather(heads, lvl_off, A, anchors, gts, gt_inds, pidx, pval, nidx
     L.check(lib.loft_rpn_sample_gather(L.arr(c_void_p, [h.data_ptr() for h in heads]), L.arr(c_int, [h.shape[2] for h in heads]),
                                        L.arr(c_int, [h.shape[3] for h in heads]), L.arr(c_int64, list(lvl_off)), Lv, B, Cp, int(A),
                                        L.ptr(anchors.float().contiguous()), L.ptr(gts.float().contiguous()), int(gts.shape[1]),
-                                       L.ptr(gt_inds.contiguous()), c_int64(gt_inds.shape[1]), L.ptr(pidx.contiguous()), L.ptr(pv), P,
+                                       L.ptr(gt_inds.contiguous()), gt_inds.shape[1], L.ptr(pidx.contiguous()), L.ptr(pv), P,
                                        L.ptr(nidx.contiguous()), L.ptr(nv), Q, L.arr(c_float, list(means)), L.arr(c_float, list(stds)),
                                        L.ptr(vals), L.ptr(rows), L.ptr(slot), L.ptr(tgt), L.ptr(label), L.ptr(weight), L.stream()),
             'loft_rpn_sample_gather')
@@ -2285,9 +2264,8 @@ def random_sample(gt_inds, num, max_pos, mode='random'):
     seed = (torch.initial_seed() * 6364136223846793005 + _SAMPLE_CALLS[0] * 1442695040888963407) & 0xFFFFFFFFFFFFFFFF
     if B > 0 and N > 0:
         ws = torch.empty(B * ((N + 15) // 16 * 16), dtype=torch.uint8, device=dev)
-        L.check(lib.loft_random_sample(L.ptr(gt_inds), B, N, int(num), int(max_pos), 0 if mode == 'first' else 1,
-                                       ctypes.c_uint64(seed), L.ptr(pidx), L.ptr(pval), L.ptr(nidx), L.ptr(nval), L.ptr(ws),
-                                       L.stream()), 'loft_random_sample')
+        L.check(lib.loft_random_sample(L.ptr(gt_inds), B, N, int(num), int(max_pos), 0 if mode == 'first' else 1, seed, L.ptr(pidx),
+                                       L.ptr(pval), L.ptr(nidx), L.ptr(nval), L.ptr(ws), L.stream()), 'loft_random_sample')
     return pidx, pval.view(torch.bool), nidx, nval.view(torch.bool)       # (the kernel writes 0 / 1 bytes: bool views, no copies)
 
 
@@ -2318,7 +2296,7 @@ def narrow_head_bwd(g, x, w, relu_in=False, need_gx=True, need_dw=True, need_db=
     dw = pooled_zeros((Cout, Cin), x.device) if need_dw else None
     db = pooled_zeros((Cout,), x.device) if need_db else None
     fn = lib.loft_narrow_head_bwd_f32 if f32 else lib.loft_narrow_head_bwd
-    L.check(fn(L.ptr(g), int(g.shape[1]), L.ptr(x), L.ptr(w2), c_int64(N * H * W), Cin, Cout, int(relu_in),
+    L.check(fn(L.ptr(g), int(g.shape[1]), L.ptr(x), L.ptr(w2), N * H * W, Cin, Cout, int(relu_in),
                L.ptr(gx), L.ptr(dw), L.ptr(db), L.stream()), 'loft_narrow_head_bwd')
     return gx, dw, db
 
@@ -2340,7 +2318,7 @@ class UnpackQueue:
         # tensors are kept referenced until the trainer has joined the two streams (no block is handed back to the main
         # stream's allocator pool while the unpack stream may still read it).
         self.main = torch.cuda.current_stream() if torch.cuda.is_available() else None
-        self.main_raw = L.stream().value if self.main is not None else None
+        self.main_raw = L.stream() if self.main is not None else None
         self.home = stream if stream is not None else self.main
         self.home_raw = self.home.cuda_stream if stream is not None else self.main_raw
         self.dedicated = stream is not None
@@ -2366,7 +2344,7 @@ class UnpackQueue:
             self._targets.add(tgt)
         self.jobs.append((dwp, db, w, bn, float(eps), slots, flat_chw, int(nsplit)))     # nsplit > 1: dwp = [nsplit][...] split-K slots
         if self.home is not None:
-            raw = L.stream().value
+            raw = L.stream()
             if raw == self.home_raw:
                 pass
             elif self.dedicated and raw == self.main_raw:
@@ -2392,7 +2370,7 @@ class UnpackQueue:
         self.keep = []
 
     def flush(self):
-        if self.home is not None and L.stream().value != self.home_raw:
+        if self.home is not None and L.stream() != self.home_raw:
             if self.main_jobs:
                 ev = torch.cuda.Event()
                 ev.record(self.main)              # everything the main stream has been handed so far (host order)
@@ -2428,8 +2406,7 @@ class UnpackQueue:
                        if r[12] < 0 or (r[12] > 1 and r[11] * r[12] <= 16384)], default=0)
             if lds > 16384:
                 raise L.LoftHipError(f'fold_unpack_bwd_multi: a record needs {lds} floats of LDS')
-            L.check(L.load().loft_fold_unpack_bwd_multi(L.ptr(desc), len(rows), c_int64(blk), int(lds), L.stream()),
-                    'loft_fold_unpack_bwd_multi')
+            L.check(L.load().loft_fold_unpack_bwd_multi(L.ptr(desc), len(rows), blk, int(lds), L.stream()), 'loft_fold_unpack_bwd_multi')
             self.jobs = []
             self._targets = set()
         done, self.done = self.done, []
@@ -2455,7 +2432,7 @@ def fold_unpack_bwd(dwp, db, w, bn=None, eps=1e-5, need_dw=True, out=None):
             g, _, m, v = [t.contiguous() for t in bn]
             dg = torch.empty(Cout, dtype=torch.float32, device=dev)
             dbeta = torch.empty(Cout, dtype=torch.float32, device=dev)
-    L.check(lib.loft_fold_unpack_bwd(L.ptr(dwp), L.ptr(db), L.ptr(w), L.ptr(g), L.ptr(m), L.ptr(v), c_float(eps), Cout, Cin,
+    L.check(lib.loft_fold_unpack_bwd(L.ptr(dwp), L.ptr(db), L.ptr(w), L.ptr(g), L.ptr(m), L.ptr(v), eps, Cout, Cin,
                                      R * S, L.ptr(dw), L.ptr(dg), L.ptr(dbeta), dwp.shape[-2], dwp.shape[-1], int(out is not None),
                                      L.stream()),
             'loft_fold_unpack_bwd')

@@ -9,6 +9,7 @@ op is called with tensors that are not on a HIP device, this module raises.
 """
 import ctypes
 import os
+import re
 
 import torch
 
@@ -44,6 +45,30 @@ def set_act16(dtype):
     return prev
 
 
+_HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'loft_hip.h')
+_CTYPES = {'int': c_int, 'int64_t': c_int64, 'uint64_t': ctypes.c_uint64, 'float': c_float}
+_prototypes = None
+
+
+def prototypes():
+    """{name: (restype, [argtypes])} of every entry point include/loft_hip.h declares, parsed once per process: the header is the
+    only place a signature is written and load_for() binds every function from it.  A pointer of any kind (device memory, host
+    array, out-parameter) is c_void_p; a type spelling the header has not used before raises instead of being guessed."""
+    global _prototypes
+    if _prototypes is None:
+        text = re.sub(r'/\*.*?\*/', ' ', open(_HEADER).read(), flags=re.S)
+        text = re.sub(r'^\s*#.*$', '', text, flags=re.M)
+        _prototypes = {}
+        for ret, name, params in re.findall(r'\b(\w+)\s+(loft_[a-z0-9_]+)\s*\(([^()]*)\)\s*;', text):
+            params = [' '.join(p.split()) for p in params.split(',')]
+            types = [ret] + [p if '*' in p else p.rpartition(' ')[0] for p in params if p != 'void']
+            if ret not in ('int', 'int64_t') or any('*' not in t and t not in _CTYPES for t in types):
+                raise LoftHipError(f'include/loft_hip.h: a type of `{ret} {name}({", ".join(params)})` is not one lib.prototypes() binds')
+            ctypes_ = [c_void_p if '*' in t else _CTYPES[t] for t in types]
+            _prototypes[name] = (ctypes_[0], ctypes_[1:])
+    return _prototypes
+
+
 def load_for(dtype):
     """The CDLL of the build whose 16-bit type is `dtype`, whatever the process's current mode (the fp32 parity mode's operand
     planes are binary16 in a bfloat16 process: both libraries are then mapped).  Raises LoftHipError when it is not built."""
@@ -55,13 +80,13 @@ def load_for(dtype):
                 f'{path} is missing: build it with `python -m bonai_amd.build` '
                 '(hipcc --offload-arch=gfx950).  bonai_amd has no CPU / eager fallback.')
         lib = ctypes.CDLL(path)
-        lib.loft_nms_workspace_bytes.restype = c_int64
-        lib.loft_nms_workspace_bytes.argtypes = [c_int64, c_int64, c_int64]
-        lib.loft_soft_nms_workspace_bytes.restype = c_int64
-        lib.loft_random_sample_workspace_bytes.restype = c_int64
-        lib.loft_conv_wgrad_patch_workspace_bytes.restype = c_int64
-        lib.loft_soft_nms_workspace_bytes.argtypes = [c_int64]
-        lib.loft_mdcn_bwd_workspace_bytes.restype = c_int64
+        for name, (restype, argtypes) in prototypes().items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:
+                raise LoftHipError(f'{path} does not export {name}, which include/loft_hip.h declares: '
+                                   'rebuild it with `python -m bonai_amd.build`') from None
+            fn.restype, fn.argtypes = restype, argtypes
         if lib.loft_act16_dtype() != _DT[dtype]:
             raise LoftHipError(f'{path} was built for another 16-bit type (loft_act16_dtype() = {lib.loft_act16_dtype()})')
         _libs[path] = lib
@@ -77,12 +102,8 @@ def load():
 
 
 def exported_symbols():
-    """Names declared in include/loft_hip.h (parsed), for the symbol-presence test."""
-    import re
-    hdr = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'loft_hip.h')
-    text = open(hdr).read()
-    text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    return sorted(set(re.findall(r'\b(loft_[a-z0-9_]+)\s*\(', text)))
+    """Names declared in include/loft_hip.h, for the symbol-presence test."""
+    return sorted(prototypes())
 
 
 def check(code, what):
@@ -91,7 +112,8 @@ def check(code, what):
 
 
 def ptr(t):
-    return c_void_p(t.data_ptr()) if t is not None else c_void_p(0)
+    """Address of a tensor's data (None: NULL) for a pointer parameter; the prototype makes it a void*."""
+    return t.data_ptr() if t is not None else None
 
 
 _DEV_INDEX = None
@@ -104,7 +126,7 @@ def stream():
     global _DEV_INDEX
     if _DEV_INDEX is None:
         _DEV_INDEX = torch.cuda.current_device()
-    return c_void_p(torch._C._cuda_getCurrentRawStream(_DEV_INDEX))
+    return torch._C._cuda_getCurrentRawStream(_DEV_INDEX)
 
 
 def dev_check(*tensors):

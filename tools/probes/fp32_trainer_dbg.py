@@ -68,7 +68,7 @@ orig_q = F2._queue_param_grads
 def q_log(jobs):
     r = orig_q(jobs)
     print('   _queue_param_grads', [(tuple(j[0].shape), tuple(j[1].shape), j[1].is_contiguous(), None if j[3] is None else tuple(j[3].shape), j[4]) for j in jobs], '->', r,
-          'stream', K.L.stream().value)
+          'stream', K.L.stream())
     return r
 F2._queue_param_grads = q_log
 run('logged')
