@@ -701,15 +701,63 @@ LOFT_EXPORT int loft_sumsq_f32(const float* g, int64_t n, float* out, void* stre
     return 0;
 }
 
-// The update body shared by sgd_kernel and sgd_scaled_kernel (so the two cannot drift).  stride / t0: the grid-stride loop's step and
+// ---- per-segment learning-rate / weight-decay multipliers (include/loft_hip.h: the segment table) ----
+// end: exclusive end offsets, ascending, end[S-1] = n; every boundary is a multiple of 8 floats, so no 16-byte group straddles two
+// segments.  end == nullptr: one segment, both multipliers 1.
+struct SegTable {
+    const long* __restrict__ end;
+    const float* __restrict__ lr_mult;
+    const float* __restrict__ wd_mult;
+    int S;
+};
+// Segment of element e.  wave_first: the element the wave's lane 0 holds in this pass -- the same number in every lane, so after
+// readfirstlane the binary search over the table is uniform: all lanes read the same entry (at most 9 cached reads for S = 512)
+// and no lane diverges.  A wave spans
+// 64 consecutive 16-byte groups (or 64 consecutive floats), which seldom crosses a boundary: each lane then walks forward from the
+// wave's segment.  The result stays inside [0, S-1] whatever the table holds.
+__device__ __forceinline__ int seg_find(const SegTable& t, long e, long wave_first) {
+    const unsigned lo32 = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long)wave_first);
+    const unsigned hi32 = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long)wave_first >> 32));
+    const long e0 = (long)(((unsigned long)hi32 << 32) | lo32);
+    int lo = 0, hi = t.S - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (e0 < t.end[mid]) hi = mid; else lo = mid + 1;
+    }
+    while (lo < t.S - 1 && e >= t.end[lo]) ++lo;
+    return lo;
+}
+
+// The update body shared by every SGD kernel (so they cannot drift).  stride / t0: the grid-stride loop's step and
 // this lane's first index, computed by the kernel itself (the launch geometry is read where the compiler knows it is uniform).
 // p, g, m: flat fp32 [n].  gnorm_sq: device scalar (sum of squares of ALL grads, after all-reduce
 // averaging).  clip = max_norm / (norm + 1e-6) if norm > max_norm else 1 (torch clip_grad_norm_).
-// torch.optim.SGD: d = g*clip + wd*p ; m = mu*m + d ; p -= lr*m   (first step m = d is the caller's
-// business: start from m = 0 and it is identical).
+// torch.optim.SGD: d = g*clip + wd*p ; m = mu*m + d ; p -= lr*m, NEST: p -= lr*(d + mu*m)   (first step m = d is the caller's
+// business: start from m = 0 and it is identical).  SEG: lr and wd are multiplied by the segment's lr_mult / wd_mult.
+// Every product, sum and FMA below is spelled out (contraction is off inside), so all instantiations round alike and the
+// table / Nesterov forms cannot differ from sgd_kernel by a compiler's choice of what to fuse.  The two spellings are the ones
+// sgd_kernel has always been compiled to, kept bit for bit: on the 16-byte body m = fma(mu, m, fma(wd, p, g*s)), on the scalar tail
+// (TAIL) m = mu*m + fma(g, s, wd*p); p = fma(-lr, m, p) on both.
+template <bool NEST, bool TAIL>
+__device__ __forceinline__ void sgd_elem(float& pv, float& mv, const float gv, const float s, const float lr, const float mu,
+                                         const float wd) {
+#pragma clang fp contract(off)
+    float d, upd;
+    if (TAIL) {
+        d = __builtin_fmaf(gv, s, wd * pv);
+        mv = mu * mv + d;
+        upd = NEST ? d + mu * mv : mv;
+    } else {
+        d = __builtin_fmaf(wd, pv, gv * s);
+        mv = __builtin_fmaf(mu, mv, d);
+        upd = NEST ? __builtin_fmaf(mu, mv, d) : mv;
+    }
+    pv = __builtin_fmaf(-lr, upd, pv);
+}
+template <bool SEG, bool NEST>
 __device__ __forceinline__ void sgd_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, long n,
                                            float gnorm_sq, float max_norm, float lr, float mu, float wd, float gscale,
-                                           const long stride, const long t0) {
+                                           const SegTable tab, const long stride, const long t0) {
     float clip = 1.f;
     if (max_norm > 0.f) {
         const float norm = sqrtf(gnorm_sq) * gscale;
@@ -722,39 +770,51 @@ __device__ __forceinline__ void sgd_update(float* __restrict__ p, const float* _
     float4* p4 = reinterpret_cast<float4*>(p);
     float4* m4 = reinterpret_cast<float4*>(m);
     const float4* g4 = reinterpret_cast<const float4*>(g);
-    auto upd = [&](float4& pv, float4& mv, const float4 gv) {
-        mv.x = mu * mv.x + (gv.x * s + wd * pv.x); pv.x -= lr * mv.x;
-        mv.y = mu * mv.y + (gv.y * s + wd * pv.y); pv.y -= lr * mv.y;
-        mv.z = mu * mv.z + (gv.z * s + wd * pv.z); pv.z -= lr * mv.z;
-        mv.w = mu * mv.w + (gv.w * s + wd * pv.w); pv.w -= lr * mv.w;
+    const long lane = threadIdx.x & 63;
+    // (lr, wd) in force for element e; first: the element of the wave's lane 0 in the same pass
+    auto rates = [&](long e, long first, float& lr_e, float& wd_e) {
+        lr_e = lr; wd_e = wd;
+        if (SEG) {
+            const int sg = seg_find(tab, e, first);
+            lr_e = lr * tab.lr_mult[sg]; wd_e = wd * tab.wd_mult[sg];
+        }
+    };
+    auto upd = [&](float4& pv, float4& mv, const float4 gv, long i) {
+        float lr_e, wd_e;
+        rates(4 * i, 4 * (i - lane), lr_e, wd_e);
+        sgd_elem<NEST, false>(pv.x, mv.x, gv.x, s, lr_e, mu, wd_e);
+        sgd_elem<NEST, false>(pv.y, mv.y, gv.y, s, lr_e, mu, wd_e);
+        sgd_elem<NEST, false>(pv.z, mv.z, gv.z, s, lr_e, mu, wd_e);
+        sgd_elem<NEST, false>(pv.w, mv.w, gv.w, s, lr_e, mu, wd_e);
     };
     long i = t0;
     for (; i + stride < n4; i += 2 * stride) {              // six loads in flight per lane (three gave 2.7 TB/s over the five streams)
         float4 pa = p4[i], ma = m4[i], pb = p4[i + stride], mb = m4[i + stride];
         const float4 ga = g4[i], gb = g4[i + stride];
-        upd(pa, ma, ga);
-        upd(pb, mb, gb);
+        upd(pa, ma, ga, i);
+        upd(pb, mb, gb, i + stride);
         m4[i] = ma; p4[i] = pa;
         m4[i + stride] = mb; p4[i + stride] = pb;
     }
     for (; i < n4; i += stride) {
         float4 pv = p4[i], mv = m4[i];
-        upd(pv, mv, g4[i]);
+        upd(pv, mv, g4[i], i);
         m4[i] = mv; p4[i] = pv;
     }
     for (long i = n4 * 4 + t0; i < n; i += stride) {
-        const float pv = p[i];
-        const float d = g[i] * s + wd * pv;
-        const float mv = mu * m[i] + d;
+        float lr_e, wd_e;
+        rates(i, i - lane, lr_e, wd_e);
+        float pv = p[i], mv = m[i];
+        sgd_elem<NEST, true>(pv, mv, g[i], s, lr_e, mu, wd_e);
         m[i] = mv;
-        p[i] = pv - lr * mv;
+        p[i] = pv;
     }
 }
 __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, long n,
                            const float* __restrict__ gnorm_sq, float max_norm, float lr, float mu, float wd,
                            float gscale) {
-    sgd_update(p, g, m, n, *gnorm_sq, max_norm, lr, mu, wd, gscale, (long)gridDim.x * blockDim.x,
-               blockIdx.x * (long)blockDim.x + threadIdx.x);
+    sgd_update<false, false>(p, g, m, n, *gnorm_sq, max_norm, lr, mu, wd, gscale, SegTable{}, (long)gridDim.x * blockDim.x,
+                             blockIdx.x * (long)blockDim.x + threadIdx.x);
 }
 LOFT_EXPORT int loft_sgd_momentum_f32(float* p, const float* g, float* m, int64_t n, const float* gnorm_sq, float max_norm,
                                       float lr, float momentum, float weight_decay, float grad_scale, void* stream) {
@@ -779,8 +839,8 @@ __global__ void sgd_scaled_kernel(float* __restrict__ p, const float* __restrict
                                   float inv_world, const float* __restrict__ state) {
     const float ss = *gnorm_sq;
     if (ls_nonfinite(ss)) return;
-    sgd_update(p, g, m, n, ss, max_norm, lr, mu, wd, inv_world * (1.0f / state[LOFT_LS_SCALE]), (long)gridDim.x * blockDim.x,
-               blockIdx.x * (long)blockDim.x + threadIdx.x);
+    sgd_update<false, false>(p, g, m, n, ss, max_norm, lr, mu, wd, inv_world * (1.0f / state[LOFT_LS_SCALE]), SegTable{},
+                             (long)gridDim.x * blockDim.x, blockIdx.x * (long)blockDim.x + threadIdx.x);
 }
 LOFT_EXPORT int loft_sgd_momentum_scaled_f32(float* p, const float* g, float* m, int64_t n, const float* gnorm_sq,
                                              float max_norm, float lr, float momentum, float weight_decay, float inv_world,
@@ -825,6 +885,169 @@ LOFT_EXPORT int loft_loss_scale_update(void* state, const float* gnorm_sq, float
                        growth_factor, backoff_factor, growth_interval, min_scale, max_scale);
     LOFT_LAUNCH_CHECK();
     return 0;
+}
+
+// ---- optimizer from the config: SGD with per-segment multipliers / Nesterov, and AdamW (include/loft_hip.h) ----
+// ls_state != nullptr: the loss-scale form -- nothing is written when gnorm_sq is not finite, gscale = inv_world / scale.
+template <bool SEG, bool NEST>
+__global__ void sgd_seg_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, long n,
+                               const float* __restrict__ gnorm_sq, float max_norm, float lr, float mu, float wd, float gscale,
+                               const SegTable tab, const float* __restrict__ ls_state) {
+    const float ss = *gnorm_sq;
+    if (ls_state) {
+        if (ls_nonfinite(ss)) return;
+        gscale = gscale * (1.0f / ls_state[LOFT_LS_SCALE]);
+    }
+    sgd_update<SEG, NEST>(p, g, m, n, ss, max_norm, lr, mu, wd, gscale, tab, (long)gridDim.x * blockDim.x,
+                          blockIdx.x * (long)blockDim.x + threadIdx.x);
+}
+LOFT_EXPORT int loft_sgd_momentum_seg_f32(float* p, const float* g, float* m, int64_t n, const float* gnorm_sq, float max_norm,
+                                          float lr, float momentum, float weight_decay, float grad_scale, int nesterov,
+                                          const int64_t* seg_end, const float* lr_mult, const float* wd_mult, int num_seg,
+                                          const void* ls_state, void* stream) {
+    if (n <= 0) return 0;
+    if (!gnorm_sq || (seg_end && (num_seg < 1 || !lr_mult || !wd_mult))) return (int)hipErrorInvalidValue;
+    const SegTable tab{(const long*)seg_end, lr_mult, wd_mult, seg_end ? num_seg : 0};
+    auto k = seg_end ? (nesterov ? sgd_seg_kernel<true, true> : sgd_seg_kernel<true, false>)
+                     : (nesterov ? sgd_seg_kernel<false, true> : sgd_seg_kernel<false, false>);
+    hipLaunchKernelGGL(k, ew_grid(n / 4), dim3(256), 0, (hipStream_t)stream, p, g, m, (long)n, gnorm_sq, max_norm, lr, momentum,
+                       weight_decay, grad_scale, tab, (const float*)ls_state);
+    LOFT_LAUNCH_CHECK();
+    return 0;
+}
+
+// torch.optim.AdamW (decoupled decay, amsgrad=False) on the arena: seven HBM streams (p, m, v read and written, g read), 28 B per
+// element.  The bias corrections of THIS step come from the optimizer-state words (computed in double by adamw_state_kernel, rounded
+// once); the wide kernel only reads them.  Per segment: decay = 1 - lr*wd, step = lr / bc1.
+struct AdamCoef { float b1, omb1, b2, omb2, eps, rbc2; };
+__device__ __forceinline__ void adamw_elem(float& pv, float& mv, float& vv, const float gv, const float s, const AdamCoef& c,
+                                           const float decay, const float step) {
+#pragma clang fp contract(off)
+    // (spelled out like sgd_elem: the table and the null-table kernel, body and tail, round alike)
+    const float gs = gv * s;
+    mv = __builtin_fmaf(c.b1, mv, c.omb1 * gs);
+    vv = __builtin_fmaf(c.b2, vv, c.omb2 * (gs * gs));
+    const float q = mv / __builtin_fmaf(sqrtf(vv), c.rbc2, c.eps);
+    pv = __builtin_fmaf(-step, q, pv * decay);
+}
+template <bool SEG>
+__global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                             long n, const float* __restrict__ gnorm_sq, float max_norm, float lr, float b1, float omb1, float b2,
+                             float omb2, float eps, float wd, float gscale, const SegTable tab,
+                             const float* __restrict__ opt_state, const float* __restrict__ ls_state) {
+    const float ss = *gnorm_sq;
+    if (ls_state) {
+        if (ls_nonfinite(ss)) return;
+        gscale = gscale * (1.0f / ls_state[LOFT_LS_SCALE]);
+    }
+    float clip = 1.f;
+    if (max_norm > 0.f) {
+        const float norm = sqrtf(ss) * gscale;
+        if (norm > max_norm) clip = max_norm / (norm + 1e-6f);
+    }
+    const float s = clip * gscale;
+    const float inv_bc1 = opt_state[LOFT_OPT_BC1_INV];
+    const AdamCoef c{b1, omb1, b2, omb2, eps, opt_state[LOFT_OPT_BC2_RSQRT]};
+    const long stride = (long)gridDim.x * blockDim.x, t0 = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    const bool al = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                      reinterpret_cast<uintptr_t>(v)) & 15) == 0;
+    const long n4 = al ? n >> 2 : 0;
+    float4* p4 = reinterpret_cast<float4*>(p);
+    float4* m4 = reinterpret_cast<float4*>(m);
+    float4* v4 = reinterpret_cast<float4*>(v);
+    const float4* g4 = reinterpret_cast<const float4*>(g);
+    const long lane = threadIdx.x & 63;
+    auto rates = [&](long e, long first, float& decay, float& step) {
+        float lr_e = lr, wd_e = wd;
+        if (SEG) {
+            const int sg = seg_find(tab, e, first);
+            lr_e = lr * tab.lr_mult[sg]; wd_e = wd * tab.wd_mult[sg];
+        }
+        decay = __builtin_fmaf(-lr_e, wd_e, 1.f);
+        step = lr_e * inv_bc1;
+    };
+    auto upd = [&](float4& pv, float4& mv, float4& vv, const float4 gv, long i) {
+        float decay, step;
+        rates(4 * i, 4 * (i - lane), decay, step);
+        adamw_elem(pv.x, mv.x, vv.x, gv.x, s, c, decay, step);
+        adamw_elem(pv.y, mv.y, vv.y, gv.y, s, c, decay, step);
+        adamw_elem(pv.z, mv.z, vv.z, gv.z, s, c, decay, step);
+        adamw_elem(pv.w, mv.w, vv.w, gv.w, s, c, decay, step);
+    };
+    long i = t0;
+    for (; i + stride < n4; i += 2 * stride) {              // eight loads in flight per lane (sgd_update's depth, one more stream)
+        float4 pa = p4[i], ma = m4[i], va = v4[i], pb = p4[i + stride], mb = m4[i + stride], vb = v4[i + stride];
+        const float4 ga = g4[i], gb = g4[i + stride];
+        upd(pa, ma, va, ga, i);
+        upd(pb, mb, vb, gb, i + stride);
+        m4[i] = ma; v4[i] = va; p4[i] = pa;
+        m4[i + stride] = mb; v4[i + stride] = vb; p4[i + stride] = pb;
+    }
+    for (; i < n4; i += stride) {
+        float4 pv = p4[i], mv = m4[i], vv = v4[i];
+        upd(pv, mv, vv, g4[i], i);
+        m4[i] = mv; v4[i] = vv; p4[i] = pv;
+    }
+    for (long i = n4 * 4 + t0; i < n; i += stride) {
+        float decay, step;
+        rates(i, i - lane, decay, step);
+        float pv = p[i], mv = m[i], vv = v[i];
+        adamw_elem(pv, mv, vv, g[i], s, c, decay, step);
+        m[i] = mv; v[i] = vv;
+        p[i] = pv;
+    }
+}
+LOFT_EXPORT int loft_adamw_f32(float* p, const float* g, float* m, float* v, int64_t n, const float* gnorm_sq, float max_norm,
+                               float lr, double beta1, double beta2, float eps, float weight_decay, float grad_scale,
+                               const int64_t* seg_end, const float* lr_mult, const float* wd_mult, int num_seg,
+                               const void* opt_state, const void* ls_state, void* stream) {
+    if (n <= 0) return 0;
+    if (!gnorm_sq || !opt_state || (seg_end && (num_seg < 1 || !lr_mult || !wd_mult)) || !(beta1 >= 0.0 && beta1 < 1.0) ||
+        !(beta2 >= 0.0 && beta2 < 1.0) || !(eps > 0.f))
+        return (int)hipErrorInvalidValue;
+    const SegTable tab{(const long*)seg_end, lr_mult, wd_mult, seg_end ? num_seg : 0};
+    // beta and 1 - beta are each rounded ONCE from the double: 1.f - (float)0.999 is off by 2e-5 relative
+    hipLaunchKernelGGL(seg_end ? adamw_kernel<true> : adamw_kernel<false>, ew_grid(n / 4), dim3(256), 0, (hipStream_t)stream, p, g, m,
+                       v, (long)n, gnorm_sq, max_norm, lr, (float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), eps,
+                       weight_decay, grad_scale, tab, (const float*)opt_state, (const float*)ls_state);
+    LOFT_LAUNCH_CHECK();
+    return 0;
+}
+
+// The optimizer-state words (LOFT_OPT_*), one lane, plain stores from a vector lane.  set_step >= 0: STEP = set_step (a new or a
+// resumed trainer).  Otherwise STEP += 1 unless the step was skipped (ls_skip and gnorm_sq not finite) -- the launch AFTER the wide
+// kernel, loss_scale_update_kernel's pattern.  Either way the bias corrections of the COMING step, t = STEP + 1, follow in double.
+__global__ void adamw_state_kernel(uint32_t* __restrict__ state, const float* __restrict__ gnorm_sq, int ls_skip, long set_step,
+                                   double beta1, double beta2) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    uint32_t step;
+    if (set_step >= 0) {
+        step = (uint32_t)set_step;
+    } else {
+        if (ls_skip && ls_nonfinite(*gnorm_sq)) return;
+        step = state[LOFT_OPT_STEP] + 1u;
+    }
+    const double t = (double)step + 1.0;
+    state[LOFT_OPT_STEP] = step;
+    state[LOFT_OPT_BC1_INV] = __float_as_uint((float)(1.0 / (1.0 - pow(beta1, t))));
+    state[LOFT_OPT_BC2_RSQRT] = __float_as_uint((float)(1.0 / sqrt(1.0 - pow(beta2, t))));
+}
+static int adamw_state_launch(void* opt_state, const float* gnorm_sq, int ls_skip, long set_step, double beta1, double beta2,
+                              void* stream) {
+    if (!opt_state || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(adamw_state_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (uint32_t*)opt_state, gnorm_sq, ls_skip,
+                       set_step, beta1, beta2);
+    LOFT_LAUNCH_CHECK();
+    return 0;
+}
+LOFT_EXPORT int loft_adamw_state_set(void* opt_state, int64_t step, double beta1, double beta2, void* stream) {
+    if (step < 0 || step > 0xffffffffLL) return (int)hipErrorInvalidValue;
+    return adamw_state_launch(opt_state, nullptr, 0, (long)step, beta1, beta2, stream);
+}
+LOFT_EXPORT int loft_adamw_state_advance(void* opt_state, const float* gnorm_sq, int skip_nonfinite, double beta1, double beta2,
+                                         void* stream) {
+    if (skip_nonfinite && !gnorm_sq) return (int)hipErrorInvalidValue;
+    return adamw_state_launch(opt_state, gnorm_sq, skip_nonfinite, -1, beta1, beta2, stream);
 }
 
 // ---- weight fold + pack (one launch per conv per step) and its chain rule -------------------------------

@@ -295,7 +295,7 @@ def step_lr(base_lr, it, epoch, warmup_iters=300, warmup_ratio=0.001, steps=(16,
 
 class Trainer:
     def __init__(self, model, lr=0.005, momentum=0.9, weight_decay=1e-4, max_norm=35.0, bucket_bytes=25 << 20,
-                 loss_scale=1.0, graph_features=False):
+                 loss_scale=1.0, graph_features=False, optimizer=None, paramwise_cfg=None):
         """loss_scale: the static scale of the reference's Fp16OptimizerHook (``fp16 = dict(loss_scale=512.)``,
         mmdet/core/fp16/hooks.py:64-96): the loss is multiplied before backward and the gradients are divided again inside
         the fused clip + SGD kernel (after the all-reduce, before the norm), exactly the hook's order.  bf16 activations have
@@ -304,7 +304,12 @@ class Trainer:
         ``'dynamic'`` or a dict (bonai_amd/loss_scale.py: init_scale, growth_factor, backoff_factor, growth_interval, min_scale,
         max_scale) selects the dynamic scaler -- an extension, the reference's hook is static-only -- with torch.amp.GradScaler's
         rule: a step whose gradients are not finite is skipped and the scale backs off, growth_interval clean steps in a row grow
-        it again.  Scale, counters and the decision live on the device (``scale_state``); the step loop still never reads back."""
+        it again.  Scale, counters and the decision live on the device (``scale_state``); the step loop still never reads back.
+
+        optimizer / paramwise_cfg: the config's ``optimizer`` dict (``type='SGD' | 'AdamW'`` with its options; it may carry its own
+        ``paramwise_cfg``) or a bonai_amd.optim.OptimSpec, and mmcv's per-parameter multipliers (bonai_amd/optim.py).  Its lr /
+        momentum / weight_decay replace the three arguments above.  Neither given: momentum SGD with one rate for the whole arena
+        through loft_sgd_momentum_f32 / loft_sgd_momentum_scaled_f32, as ever.  max_norm=None: no gradient clip."""
         self.model = model
         # graph_features: backbone + neck forward and backward as two hipGraphs, recorded at the third step and replayed from
         # then on (bonai_amd/graphs.py); fixed-size batches only.  Capture failures fall back to eager launches, loudly.
@@ -312,7 +317,15 @@ class Trainer:
         self._fgraphs = None
         self._unpack_stream = None
         self._steps_run = 0          # steps THIS trainer has run (a resumed trainer starts at iter > 0 with an empty prepack registry)
-        self.lr, self.mu, self.wd, self.max_norm = lr, momentum, weight_decay, max_norm
+        self.lr, self.mu, self.wd, self.max_norm = lr, momentum, weight_decay, (0.0 if max_norm is None else max_norm)
+        self.optim = None
+        if optimizer is not None or paramwise_cfg is not None:
+            from .optim import build_spec
+            if optimizer is None:
+                optimizer = dict(type='SGD', lr=lr, momentum=momentum, weight_decay=weight_decay)
+            self.optim = build_spec(optimizer, paramwise_cfg, model)
+            h = self.optim.hyper
+            self.lr, self.mu, self.wd = h['lr'], h.get('momentum', 0.0), h['weight_decay']
         mode, parsed = parse_loss_scale(loss_scale)
         # static: the float, used exactly as before.  dynamic: None -- the scale is a device value, see loss_scale_state()
         self.loss_scale = parsed if mode == 'static' else None
@@ -328,6 +341,22 @@ class Trainer:
             # so a replay sees the current scale and nothing of it is baked into a graph -- the combination is allowed.
             self.scale_state = K.loss_scale_state_pack(self.scaler['init_scale']).to(self.arena.data.device)
             self._scale = self.scale_state[K.LS_SCALE]      # 0-dim VIEW of the state's scale: the loss's multiplier
+        # The config's optimizer.  seg_table: per-segment multipliers, uploaded here once (None: all 1).  AdamW: arena.momentum is
+        # exp_avg, and a second state buffer (exp_avg_sq) plus the device-side step count exist only then.
+        self.seg_table = self.opt_state = self.exp_avg_sq = None
+        self._plain_sgd = True
+        if self.optim is not None:
+            from .optim import arena_segments
+            name = {id(p): n for n, p in model.named_parameters()}
+            a = self.arena
+            segs = arena_segments(self.optim, [(name[id(p)], a.offsets[id(p)], (p.numel() + 7) // 8 * 8) for p in a.order])
+            if segs is not None:
+                self.seg_table = K.SegmentTable(segs, a.numel, a.data.device)
+            self._plain_sgd = self.optim.rule == 'SGD' and not self.optim.hyper['nesterov'] and segs is None
+            if self.optim.rule == 'AdamW':
+                self.exp_avg_sq = torch.zeros_like(a.momentum)
+                if a.data.is_cuda:
+                    self.opt_state = K.adamw_state_new(0, *self.optim.hyper['betas'], a.data.device)
         self.iter = 0
         self.prepack = K.PrepackRegistry()
         # kernels accumulate weight / BN gradients straight into the arena slots (bonai_amd.nn.GRAD_SINK); the callback
@@ -356,6 +385,51 @@ class Trainer:
         if fg.ready:
             self.model.feat_provider = fg.provider
 
+    def _config_optimizer_step(self, lr):
+        """The update of a trainer whose optimizer comes from the config and is not plain momentum SGD: one wide launch (plus
+        AdamW's one-lane step count).  Dynamic loss scaling: both read the scale state and skip on overflow, as the plain path."""
+        a, o, c = self.arena, self.optim, self.scaler
+        gscale = 1.0 / self.world if c is not None else 1.0 / (self.world * self.loss_scale)
+        if o.rule == 'SGD':
+            K.sgd_momentum_seg_(a.data, a.grad, a.momentum, self.gnorm_sq, self.max_norm, lr, self.mu, self.wd, grad_scale=gscale,
+                                nesterov=o.hyper['nesterov'], table=self.seg_table, ls_state=self.scale_state)
+        else:
+            b1, b2 = o.hyper['betas']
+            K.adamw_(a.data, a.grad, a.momentum, self.exp_avg_sq, self.gnorm_sq, self.max_norm, lr, b1, b2, o.hyper['eps'], self.wd,
+                     self.opt_state, grad_scale=gscale, table=self.seg_table, ls_state=self.scale_state)
+            K.adamw_state_advance_(self.opt_state, self.gnorm_sq, b1, b2, skip_nonfinite=c is not None)
+        if c is not None:
+            K.loss_scale_update_(self.scale_state, self.gnorm_sq, 1.0 / self.world, c['growth_factor'], c['backoff_factor'],
+                                 c['growth_interval'], c['min_scale'], c['max_scale'])
+
+    def _param_groups(self, base):
+        """``base``: one torch param group without 'params'.  -> the group list: one group over all parameters, or -- with a
+        paramwise_cfg -- one per parameter with its own lr / weight_decay, as mmcv's DefaultOptimizerConstructor builds them."""
+        named = list(self.model.named_parameters())
+        if self.optim is None or not self.optim.paramwise:
+            return [dict(base, params=list(range(len(named))))]
+        groups = []
+        for i, (n, p) in enumerate(named):
+            lm, dm = self.optim.mult_of(n) if p.requires_grad else (1.0, 1.0)
+            groups.append(dict(base, lr=base['lr'] * lm, weight_decay=base['weight_decay'] * dm, params=[i]))
+        return groups
+
+    def _adamw_state_dict(self):
+        a, h = self.arena, self.optim.hyper
+        idx = {id(p): i for i, p in enumerate(self.model.parameters())}
+        state = {}
+        if self.iter > 0:
+            step = float(K.adamw_state_step(self.opt_state))        # the ONE read-back of the device-side step count
+            for p in a.params:
+                o = a.offsets[id(p)]
+                state[idx[id(p)]] = dict(step=torch.tensor(step),
+                                         exp_avg=a.momentum[o:o + p.numel()].view(p.shape).detach().cpu().clone(),
+                                         exp_avg_sq=self.exp_avg_sq[o:o + p.numel()].view(p.shape).detach().cpu().clone())
+        # the group keys of the installed torch.optim.AdamW (they differ between torch versions), with this trainer's values
+        probe = torch.optim.AdamW([torch.zeros(1)], lr=h['lr'], betas=h['betas'], eps=h['eps'], weight_decay=h['weight_decay'])
+        base = {k: v for k, v in probe.state_dict()['param_groups'][0].items() if k != 'params'}
+        return state, self._param_groups(base)
+
     def optimizer_state_dict(self):
         """The arena's SGD state in torch.optim.SGD.state_dict() layout (what mmcv's CheckpointHook stores under 'optimizer',
         apis/train.py:139-140 resumes from): parameters indexed in ``model.parameters()`` order (frozen ones included, as the
@@ -364,15 +438,18 @@ class Trainer:
         state, idx = {}, {}
         for i, p in enumerate(self.model.parameters()):
             idx[id(p)] = i
-        if self.iter > 0:
-            for p in a.params:
-                o = a.offsets[id(p)]
-                state[idx[id(p)]] = dict(momentum_buffer=a.momentum[o:o + p.numel()].view(p.shape).detach().cpu().clone())
-        group = dict(lr=self.lr, momentum=self.mu, dampening=0, weight_decay=self.wd, nesterov=False,
-                     params=list(range(len(idx))))
+        if self.optim is not None and self.optim.rule == 'AdamW':
+            state, groups = self._adamw_state_dict()
+        else:
+            if self.iter > 0:
+                for p in a.params:
+                    o = a.offsets[id(p)]
+                    state[idx[id(p)]] = dict(momentum_buffer=a.momentum[o:o + p.numel()].view(p.shape).detach().cpu().clone())
+            groups = self._param_groups(dict(lr=self.lr, momentum=self.mu, dampening=0, weight_decay=self.wd,
+                                             nesterov=bool(self.optim is not None and self.optim.hyper['nesterov'])))
         # sampler_calls: the RandomSampler kernel's draws are a function of (torch.initial_seed(), call count); a resumed run
         # continues the uninterrupted run's sequence only if the count travels with the optimizer state
-        sd = dict(state=state, param_groups=[group], iter=self.iter, sampler_calls=int(K._SAMPLE_CALLS[0]))
+        sd = dict(state=state, param_groups=groups, iter=self.iter, sampler_calls=int(K._SAMPLE_CALLS[0]))
         if self.scaler is not None:                       # (dynamic mode only: the static layout is what the reference stores)
             sd['loss_scaler'] = self.loss_scale_state()
         return sd
@@ -398,21 +475,34 @@ class Trainer:
         if groups and sum(len(g.get('params', ())) for g in groups) != len(params):
             raise RuntimeError(f"optimizer state covers {sum(len(g['params']) for g in groups)} parameters, the model has "
                                f'{len(params)}: it was written for a different model')
-        todo = []
+        mine = 'AdamW' if (self.optim is not None and self.optim.rule == 'AdamW') else 'SGD'
+        theirs = 'AdamW' if (any('betas' in g for g in groups or ()) or any('exp_avg' in st for st in state.values())) else 'SGD'
+        if mine != theirs:
+            raise RuntimeError(f'optimizer state of {theirs} cannot be loaded into a trainer whose optimizer is {mine}: '
+                               'the two rules keep different state')
+        first, second = ('exp_avg', 'exp_avg_sq') if mine == 'AdamW' else ('momentum_buffer', None)
+        todo, steps = [], set()
         for i, st in state.items():
             if not 0 <= int(i) < len(params):
                 raise RuntimeError(f'optimizer state index {i} outside the model\'s {len(params)} parameters')
             p = params[int(i)]
-            buf = st.get('momentum_buffer')
-            if buf is None:
-                continue
-            if tuple(buf.shape) != tuple(p.shape):
-                raise RuntimeError(f'optimizer state {i}: momentum_buffer {tuple(buf.shape)} does not fit parameter '
-                                   f'{tuple(p.shape)} (parameter order differs from the checkpoint\'s)')
-            if id(p) in a.offsets:
-                todo.append((a.offsets[id(p)], p.numel(), buf))
-        for o, n, buf in todo:                              # (nothing is written unless everything fits)
-            a.momentum[o:o + n].copy_(buf.reshape(-1).to(a.momentum.device))
+            for key, dst in ((first, a.momentum), (second, self.exp_avg_sq)):
+                buf = st.get(key) if key else None
+                if buf is None:
+                    continue
+                if tuple(buf.shape) != tuple(p.shape):
+                    raise RuntimeError(f'optimizer state {i}: {key} {tuple(buf.shape)} does not fit parameter '
+                                       f'{tuple(p.shape)} (parameter order differs from the checkpoint\'s)')
+                if id(p) in a.offsets:
+                    todo.append((dst, a.offsets[id(p)], p.numel(), buf))
+            if mine == 'AdamW' and id(p) in a.offsets and 'step' in st:
+                steps.add(int(st['step']))
+        if len(steps) > 1:
+            raise RuntimeError(f'AdamW state with different step counts per parameter {sorted(steps)[:4]}: the arena keeps one')
+        for dst, o, n, buf in todo:                         # (nothing is written unless everything fits)
+            dst[o:o + n].copy_(buf.reshape(-1).to(dst.device))
+        if mine == 'AdamW' and steps:
+            self.opt_state.copy_(K.adamw_state_new(steps.pop(), *self.optim.hyper['betas'], self.opt_state.device))
         self.iter = int(sd.get('iter', self.iter))
         if 'sampler_calls' in sd:
             K._SAMPLE_CALLS[0] = int(sd['sampler_calls'])
@@ -492,7 +582,9 @@ class Trainer:
         self.reducer.finish()
         self.gnorm_sq.zero_()
         K.sumsq_(self.arena.grad, self.gnorm_sq)
-        if self.scaler is None:
+        if not self._plain_sgd:
+            self._config_optimizer_step(self.lr if lr is None else lr)
+        elif self.scaler is None:
             K.sgd_momentum_(self.arena.data, self.arena.grad, self.arena.momentum, self.gnorm_sq, self.max_norm,
                             self.lr if lr is None else lr, self.mu, self.wd, grad_scale=1.0 / (self.world * self.loss_scale))
         else:

@@ -1322,6 +1322,96 @@ def loss_scale_update_(state, gnorm_sq, inv_world, growth_factor, backoff_factor
                                        min_scale, max_scale, L.stream()), 'loft_loss_scale_update')
 
 
+# ---- optimizer from the config: the segment table and the AdamW step state of include/loft_hip.h (LOFT_OPT_*)
+OPT_STEP, OPT_BC1_INV, OPT_BC2_RSQRT, OPT_WORDS = 0, 1, 2, 4
+
+
+class SegmentTable:
+    """Per-segment (lr_mult, wd_mult) over a flat arena of ``n`` floats, uploaded ONCE (three small device tensors).
+    ``segments``: [(end, lr_mult, wd_mult)] with exclusive ends, ascending, the inner ones multiples of 8 (no 16-byte group may
+    straddle two segments), the last one equal to n -- checked here, on the host values, because the kernels trust the table."""
+
+    def __init__(self, segments, n, device):
+        ends = [int(s[0]) for s in segments]
+        if not ends or ends[-1] != n or any(e % 8 for e in ends[:-1]) or any(b <= a for a, b in zip([0] + ends, ends)):
+            raise L.LoftHipError(f'segment ends must be ascending multiples of 8 ending at n = {n}: {ends[:4]}...{ends[-2:]}')
+        self.n, self.segments = int(n), [(int(e), float(a), float(b)) for e, a, b in segments]
+        self.end = torch.tensor(ends, dtype=torch.int64).to(device)
+        self.lr_mult = torch.tensor([s[1] for s in self.segments], dtype=torch.float32).to(device)
+        self.wd_mult = torch.tensor([s[2] for s in self.segments], dtype=torch.float32).to(device)
+
+    def __len__(self):
+        return len(self.segments)
+
+
+def _seg_args(table, p):
+    if table is None:
+        return None, None, None, 0
+    if table.n != p.numel():
+        raise L.LoftHipError(f'the segment table covers {table.n} floats, the arena has {p.numel()}')
+    L.dev_check(table.end, table.lr_mult, table.wd_mult)
+    return L.ptr(table.end), L.ptr(table.lr_mult), L.ptr(table.wd_mult), len(table)
+
+
+def sgd_momentum_seg_(p, g, m, gnorm_sq, max_norm, lr, momentum, weight_decay, grad_scale=1.0, nesterov=False, table=None,
+                      ls_state=None):
+    """sgd_momentum_ with per-segment multipliers (``table``: SegmentTable | None) and Nesterov momentum.  ``ls_state``: the loss
+    scaler's state -- then ``grad_scale`` is inv_world and the whole update is skipped when ``gnorm_sq`` is not finite."""
+    lib = L.load()
+    L.dev_check(p, g, m, gnorm_sq, ls_state)
+    if ls_state is not None:
+        _ls_state_check(ls_state)
+    end, lrm, wdm, S = _seg_args(table, p)
+    L.check(lib.loft_sgd_momentum_seg_f32(L.ptr(p), L.ptr(g), L.ptr(m), p.numel(), L.ptr(gnorm_sq), max_norm, lr, momentum, weight_decay,
+                                          grad_scale, int(bool(nesterov)), end, lrm, wdm, S, L.ptr(ls_state), L.stream()),
+            'loft_sgd_momentum_seg_f32')
+
+
+def _opt_state_check(state):
+    if state.dtype != torch.float32 or state.numel() != OPT_WORDS or not state.is_contiguous():
+        raise L.LoftHipError(f'the optimizer step state is a contiguous float32 tensor of {OPT_WORDS} words')
+
+
+def adamw_state_new(step, beta1, beta2, device):
+    """-> the AdamW step state on ``device``: ``step`` applied steps so far, bias corrections of the coming step."""
+    lib = L.load()
+    state = torch.zeros(OPT_WORDS, dtype=torch.float32, device=device)
+    L.dev_check(state)
+    L.check(lib.loft_adamw_state_set(L.ptr(state), int(step), beta1, beta2, L.stream()), 'loft_adamw_state_set')
+    return state
+
+
+def adamw_state_step(state):
+    """Applied steps so far (one device-to-host copy: for checkpoints only)."""
+    return int(state.detach().cpu().view(torch.int32)[OPT_STEP]) & 0xffffffff
+
+
+def adamw_(p, g, m, v, gnorm_sq, max_norm, lr, beta1, beta2, eps, weight_decay, opt_state, grad_scale=1.0, table=None,
+           ls_state=None):
+    """torch.optim.AdamW's step on the flat arena at t = (steps in ``opt_state``) + 1; only reads ``opt_state``.  Follow it with
+    adamw_state_advance_ on the same stream.  ``table`` / ``ls_state`` as in sgd_momentum_seg_."""
+    lib = L.load()
+    L.dev_check(p, g, m, v, gnorm_sq, opt_state, ls_state)
+    _opt_state_check(opt_state)
+    if ls_state is not None:
+        _ls_state_check(ls_state)
+    if not (g.numel() == m.numel() == v.numel() == p.numel()):
+        raise L.LoftHipError('adamw_: p, g, m, v differ in size')
+    end, lrm, wdm, S = _seg_args(table, p)
+    L.check(lib.loft_adamw_f32(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), L.ptr(gnorm_sq), max_norm, lr, beta1, beta2, eps,
+                               weight_decay, grad_scale, end, lrm, wdm, S, L.ptr(opt_state), L.ptr(ls_state), L.stream()),
+            'loft_adamw_f32')
+
+
+def adamw_state_advance_(opt_state, gnorm_sq, beta1, beta2, skip_nonfinite=False):
+    """Count the step adamw_ just applied -- unless ``skip_nonfinite`` and ``gnorm_sq`` is not finite (adamw_ skipped it)."""
+    lib = L.load()
+    L.dev_check(opt_state, gnorm_sq)
+    _opt_state_check(opt_state)
+    L.check(lib.loft_adamw_state_advance(L.ptr(opt_state), L.ptr(gnorm_sq), int(bool(skip_nonfinite)), beta1, beta2, L.stream()),
+            'loft_adamw_state_advance')
+
+
 # ------------------------------------------------------------------ boxes / targets
 
 def iou_assign(boxes, nbox, gts, ngt, pos_thr, neg_thr, min_pos, low_quality=True):

@@ -46,7 +46,7 @@ def set_act16(dtype):
 
 
 _HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'loft_hip.h')
-_CTYPES = {'int': c_int, 'int64_t': c_int64, 'uint64_t': ctypes.c_uint64, 'float': c_float}
+_CTYPES = {'int': c_int, 'int64_t': c_int64, 'uint64_t': ctypes.c_uint64, 'float': c_float, 'double': ctypes.c_double}
 _prototypes = None
 
 

@@ -491,6 +491,43 @@ int loft_sgd_momentum_scaled_f32(float* p, const float* g, float* m, int64_t n, 
                                  void* stream);
 int loft_loss_scale_update(void* state, const float* gnorm_sq, float inv_world, float growth_factor, float backoff_factor,
                            int growth_interval, float min_scale, float max_scale, void* stream);
+/* Optimizer from the config (cfg.optimizer / paramwise_cfg, bonai_amd/optim.py): SGD with per-segment multipliers and
+ * Nesterov momentum, and AdamW, on the same flat fp32 arena and with loft_sgd_momentum_f32's prologue (gnorm_sq, max_norm
+ * <= 0 disables the clip, clip = max_norm / (norm + 1e-6), grad_scale).  NOT in the reference, whose schedules are
+ * momentum SGD with one rate for all parameters.
+ * Segment table: num_seg segments in device memory -- seg_end int64 [num_seg] exclusive end offsets, ascending, the last
+ *   one equal to n; lr_mult, wd_mult fp32 [num_seg].  Every boundary is a multiple of 8 floats (the arena pads each slot
+ *   to 8), so no 16-byte access straddles two segments.  Segment s runs with lr * lr_mult[s] and weight_decay * wd_mult[s].
+ *   seg_end = NULL: one segment, both multipliers 1 (num_seg and the other two pointers are ignored).
+ * Loss-scale form: ls_state != NULL is the LOFT_LS_* state above; then grad_scale is inv_world, the gradient scale is
+ *   inv_world * (1 / state[SCALE]), and when *gnorm_sq is not finite NOTHING is written (p, m, v, the step count).
+ * sgd_momentum_seg: d = g*s + wd*p ; m = mu*m + d ; p -= lr*m, nesterov != 0: p -= lr*(d + mu*m) (torch.optim.SGD,
+ *   dampening 0).  The update body is loft_sgd_momentum_f32's: with seg_end = NULL and nesterov = 0 the results are
+ *   bit-identical to it.
+ * adamw: torch.optim.AdamW (decoupled decay, amsgrad=False) at step t = STEP + 1:
+ *   p *= 1 - lr*wd ; m = b1*m + (1-b1)*g*s ; v = b2*v + (1-b2)*(g*s)^2 ; p -= (lr / bc1) * m / (sqrt(v)/sqrt(bc2) + eps),
+ *   bc1 = 1 - b1^t, bc2 = 1 - b2^t.  28 B of traffic per element (p, m, v read and written, g read); SGD is 20 B.
+ *   opt_state: LOFT_OPT_WORDS 32-bit words in device memory -- STEP uint32 applied steps so far | BC1_INV fp32 1 / bc1 |
+ *   BC2_RSQRT fp32 1 / sqrt(bc2), both for the COMING step, computed in double and rounded once | word 3 reserved.
+ *   The wide kernel only reads it.  beta1, beta2 are doubles: beta and 1 - beta are each rounded to fp32 once.
+ * adamw_state_set: STEP = step and the two corrections for step + 1 (a new trainer: step 0; a resumed one: its count).
+ * adamw_state_advance: one launch AFTER adamw on the same stream: STEP += 1 and the next corrections, unless
+ *   skip_nonfinite != 0 and *gnorm_sq is not finite (the step adamw skipped: t does not advance, as GradScaler skips
+ *   optimizer.step()).  The step count lives on the device because the host never learns whether a step was skipped. */
+#define LOFT_OPT_STEP 0
+#define LOFT_OPT_BC1_INV 1
+#define LOFT_OPT_BC2_RSQRT 2
+#define LOFT_OPT_WORDS 4
+int loft_sgd_momentum_seg_f32(float* p, const float* g, float* m, int64_t n, const float* gnorm_sq, float max_norm, float lr,
+                              float momentum, float weight_decay, float grad_scale, int nesterov, const int64_t* seg_end,
+                              const float* lr_mult, const float* wd_mult, int num_seg, const void* ls_state, void* stream);
+int loft_adamw_f32(float* p, const float* g, float* m, float* v, int64_t n, const float* gnorm_sq, float max_norm, float lr,
+                   double beta1, double beta2, float eps, float weight_decay, float grad_scale, const int64_t* seg_end,
+                   const float* lr_mult, const float* wd_mult, int num_seg, const void* opt_state, const void* ls_state,
+                   void* stream);
+int loft_adamw_state_set(void* opt_state, int64_t step, double beta1, double beta2, void* stream);
+int loft_adamw_state_advance(void* opt_state, const float* gnorm_sq, int skip_nonfinite, double beta1, double beta2,
+                             void* stream);
 
 /* ---- box / target arithmetic (fp32 + integer) -------------------------------------------------
  * iou_assign: MaxIoUAssigner.assign (mmdet/core/bbox/assigners/max_iou_assigner.py:60-212 with

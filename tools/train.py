@@ -32,6 +32,20 @@ def parse_option(opt):
         return k, v
 
 
+def optimizer_kwargs(cfg, model, options=(), verbose=False):
+    """Trainer's optimizer arguments from cfg.optimizer (type, options, paramwise_cfg) and cfg.optimizer_config.grad_clip
+    (bonai_amd/optim.py); needs no device.  ``--options optimizer.type=X`` over a config written for the other rule leaves that
+    rule's own options behind (SGD's momentum under AdamW): those are dropped, and named on stdout."""
+    from bonai_amd.optim import drop_foreign_options, trainer_kwargs
+    if any(o.split('=', 1)[0] == 'optimizer.type' for o in options):
+        kept, dropped = drop_foreign_options(cfg.optimizer)
+        if dropped:
+            cfg.optimizer = kept
+            if verbose:
+                print(f"optimizer.type={kept['type']} given on the command line: dropped the config's {dropped}", flush=True)
+    return trainer_kwargs(cfg, model)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('config')
@@ -72,8 +86,7 @@ def main():
     model = build_detector(cfg.model, train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg).cuda().train()
     if args.load_from:
         load_checkpoint(model, args.load_from, strict=False)
-    tr = Trainer(model, lr=cfg.optimizer.lr, momentum=cfg.optimizer.momentum, weight_decay=cfg.optimizer.weight_decay,
-                 max_norm=cfg.optimizer_config.grad_clip.max_norm,
+    tr = Trainer(model, **optimizer_kwargs(cfg, model, args.options, verbose=rank == 0),
                  loss_scale=(cfg.get('fp16') or {}).get('loss_scale', 1.0), graph_features=args.graph)
     start_iter = 0
     if args.resume_from:                                   # mmcv runner.resume: weights + optimizer state + iter / epoch
