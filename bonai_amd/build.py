@@ -24,6 +24,7 @@ FLAGS = {
     'nms.hip': ['-ffp-contract=off'],
     'boxes.hip': ['-ffp-contract=off'],
     'deform.hip': ['-ffp-contract=off'],
+    'augment.hip': ['-ffp-contract=off'],      # Normalize as subtract, then divide: bit for bit the torch chain
 }
 
 

@@ -14,6 +14,8 @@ import math
 import numpy as np
 import torch
 
+from .kernels import D4_MIRROR_X, D4_MIRROR_Y, D4_TRANSPOSE
+
 
 def parse_bonai_annotations(img_info, ann_info, cat_ids=(1,), cat2label=None, bbox_type='roof', mask_type='roof',
                             offset_coordinate='rectangle', resolution=0.6, ignore_buildings=True):
@@ -146,15 +148,201 @@ def flip_sample(sample, direction='horizontal', defer_image=False):
     return out
 
 
+RIGHT_ANGLES = (0, 90, 180, 270)
+_WHY_RIGHT_ANGLES = (
+    'RandomRotate is supported for the angles 0, 90, 180 and 270 only (got {got}).  For any other angle the reference has '
+    'nothing sound to mirror: its bbox_rotate (transforms.py:1975-2014) shifts the boxes by (nW/2 - cx, nH/2 - cy), the offset of '
+    'an EXPANDED canvas, while the image is rotated with auto_bound=False and is not expanded -- the boxes do not lie on the '
+    "reference's own image (212 px off at 45 degrees on a 1024 tile).  choice='any' (a string: range(0, 359)) is such a choice.")
+
+
+def check_rotate_angles(angles):
+    """The angles of a RandomRotate ``choice`` as a tuple of ints; NotImplementedError (with the reason) unless every one of them
+    is a right angle.  A string is the reference's 'any' (transforms.py:1853-1854)."""
+    if isinstance(angles, str) or not isinstance(angles, (list, tuple)):
+        raise NotImplementedError(_WHY_RIGHT_ANGLES.format(got=repr(angles)))
+    for a in angles:
+        if isinstance(a, (bool, str)) or a not in RIGHT_ANGLES:
+            raise NotImplementedError(_WHY_RIGHT_ANGLES.format(got=repr(tuple(angles))))
+    return tuple(int(a) for a in angles)
+
+
+def _rotation_matrix(center, angle, scale=1.0):
+    """cv2.getRotationMatrix2D from OpenCV's documented formula (cv2 is not a dependency): with a = scale * cos(angle) and
+    b = scale * sin(angle), angle in degrees, [[a, b, (1 - a) * cx - b * cy], [-b, a, b * cx + (1 - a) * cy]] in float64."""
+    rad = angle * math.pi / 180.0
+    a, b = scale * math.cos(rad), scale * math.sin(rad)
+    cx, cy = center
+    return np.array([[a, b, (1 - a) * cx - b * cy], [-b, a, b * cx + (1 - a) * cy]], dtype=np.float64)
+
+
+def rotate_bboxes(bboxes, img_shape, angle):
+    """RandomRotate.bbox_rotate (transforms.py:1975-2014), get_corners (:1862-1898) included: the four corners of every box (the
+    second and third rebuilt from x1 + width, y1 + height in the boxes' own dtype, as there), times the float64 matrix about
+    (w / 2, h / 2) with -angle, cast to float32, then min / max per box.
+
+    The reference's half-pixel quirk is kept and is consistent: boxes are in pixel-EDGE coordinates, so turning them about
+    w / 2 is turning the pixel centres about (w - 1) / 2, which is what mmcv.imrotate does to the image.  The reference also
+    re-centres on an expanded canvas (nW, nH) although the image is not expanded; for the supported angles on a square tile
+    nW == w and nH == h and the shift is zero (see ``check_rotate_angles`` for the others)."""
+    angle, = check_rotate_angles((angle,))
+    bboxes = np.asarray(bboxes)
+    assert bboxes.shape[-1] % 4 == 0
+    if bboxes.shape[0] == 0:
+        return bboxes
+    h, w = img_shape[:2]
+    if angle in (90, 270) and h != w:
+        raise NotImplementedError(f'RandomRotate by {angle} needs a square tile, got {w}x{h}: the rotated image is not expanded')
+    x1, y1 = bboxes[:, 0].reshape(-1, 1), bboxes[:, 1].reshape(-1, 1)
+    width, height = (bboxes[:, 2] - bboxes[:, 0]).reshape(-1, 1), (bboxes[:, 3] - bboxes[:, 1]).reshape(-1, 1)
+    corners = np.hstack((x1, y1, x1 + width, y1, x1, y1 + height, bboxes[:, 2].reshape(-1, 1), bboxes[:, 3].reshape(-1, 1)))
+    corners = np.hstack((corners, bboxes[:, 4:])).reshape(-1, 2)
+    corners = np.hstack((corners, np.ones((corners.shape[0], 1), dtype=corners.dtype)))
+    cx, cy = w / 2, h / 2
+    M = _rotation_matrix((cx, cy), -angle, 1.0)
+    cos, sin = np.abs(M[0, 0]), np.abs(M[0, 1])
+    M[0, 2] += int(h * sin + w * cos) / 2 - cx
+    M[1, 2] += int(h * cos + w * sin) / 2 - cy
+    calc = np.array(np.dot(M, corners.T).T, dtype=np.float32).reshape(-1, 8)
+    xs, ys = calc[:, [0, 2, 4, 6]], calc[:, [1, 3, 5, 7]]
+    return np.hstack((xs.min(1).reshape(-1, 1), ys.min(1).reshape(-1, 1), xs.max(1).reshape(-1, 1), ys.max(1).reshape(-1, 1)))
+
+
+def rotate_offsets(offsets, angle):
+    """RandomRotate.offset_rotate (transforms.py:1957-1964): per offset a polar round trip -- length = math.sqrt(x**2 + y**2) and
+    math.atan2(y, x) on the float32 elements, the angle plus angle * pi / 180, length * np.cos / np.sin in float64 -- then the
+    float32 cast.  Deliberately NOT a sign swap: cos(pi / 2) is 6e-17, and what of 6e-17 * length survives the cast survives
+    here as it does there (a rotated (0, y) has x = 6e-17 * y, not 0)."""
+    angle, = check_rotate_angles((angle,))
+    out = []
+    for ox, oy in np.asarray(offsets, dtype=np.float32).reshape(-1, 2):
+        length, phi = math.sqrt(ox ** 2 + oy ** 2), math.atan2(oy, ox) + angle * math.pi / 180.0
+        out.append([length * np.cos(phi), length * np.sin(phi)])
+    return np.array(out, dtype=np.float32).reshape(-1, 2)
+
+
+# ---- the eight symmetries of the square ------------------------------------------------------------------------------------------
+# RandomFlip and right-angle RandomRotate, in any order and number, compose to ONE element: an optional transpose, then an optional
+# x-mirror, then an optional y-mirror (include/loft_hip.h LOFT_D4_*: 1, 2, 4).  The rule for the angle: mmcv.imrotate(img, angle,
+# auto_bound=False) turns about ((w - 1) / 2, (h - 1) / 2) with cv2.getRotationMatrix2D(center, -angle, 1); from OpenCV's
+# documented matrix, source pixel (x, y) lands at (S-1-y, x) for 90, (S-1-x, S-1-y) for 180, (y, S-1-x) for 270 -- an exact
+# pixel permutation, np.rot90(a, k=-angle // 90): clockwise for a positive angle.  cv2 and mmcv are not installed where this was
+# written, so that equality is DERIVED from the documentation and has not been run against them.
+
+
+def d4_apply(a, elem, axes=(0, 1)):
+    """numpy view of ``a`` under an element, rows = axes[0], columns = axes[1] (the definition the kernels are tested against)."""
+    ay, ax = axes
+    if elem & D4_TRANSPOSE:
+        a = np.swapaxes(a, ay, ax)
+    if elem & D4_MIRROR_X:
+        a = np.flip(a, ax)
+    if elem & D4_MIRROR_Y:
+        a = np.flip(a, ay)
+    return a
+
+
+def _d4_op(a, op, axes=(0, 1)):
+    """One recorded operation -- 'horizontal', 'vertical' or a right angle -- on a numpy array."""
+    if op == 'horizontal':
+        return np.flip(a, axes[1])
+    if op == 'vertical':
+        return np.flip(a, axes[0])
+    if isinstance(op, str):
+        raise ValueError(f"Invalid flipping direction '{op}'")
+    angle, = check_rotate_angles((op,))
+    return np.rot90(a, k=-angle // 90, axes=axes)
+
+
+_D4_PROBE = np.arange(4).reshape(2, 2)
+_D4_OF = {d4_apply(_D4_PROBE, e).tobytes(): e for e in range(8)}      # a 2 x 2 array tells the eight elements apart
+
+
+def d4_compose(ops):
+    """The ordered record of flips and right-angle rotations (what ``img_flip`` / ``mask_flips`` hold) -> the one element that
+    does the same.  Flips and rotations do not commute; the record is applied to a 2 x 2 probe in order and looked up."""
+    p = _D4_PROBE
+    for op in ops:
+        p = _d4_op(p, op)
+    return _D4_OF[np.ascontiguousarray(p).tobytes()]
+
+
+def _carries_rotation(ops):
+    return any(not isinstance(op, str) for op in ops)
+
+
+def rotate_sample(sample, angle, defer_image=False):
+    """One training sample rotated as RandomRotate.__call__ does (transforms.py:2016-2092), for a right angle on a square tile
+    (``check_rotate_angles`` says why no other).  Shaped like ``flip_sample``: host bitmaps are turned with np.rot90; a sample
+    that carries ``gt_polygons`` records the angle in ``mask_flips`` -- the reference rasterises first and permutes the BITMAP,
+    and so does ``to_device_batch`` --; ``defer_image`` records it in ``img_flip`` for the device.  The record is ordered: a
+    flip before a rotation is not the rotation before the flip.
+
+    Angle 0 with rotate=True leaves the pixels alone (nothing is recorded) but, as in the reference, still sends boxes and
+    offsets through bbox_rotate / offset_rotate, and ``rotate`` stays True in the meta."""
+    angle, = check_rotate_angles((angle,))
+    h, w = sample['img'].shape[:2]
+    if angle in (90, 270) and h != w:
+        raise NotImplementedError(f'RandomRotate by {angle} needs a square tile, got {w}x{h}: the rotated image is not expanded')
+    k = -angle // 90
+    out = dict(sample)
+    if angle:
+        if defer_image:
+            out['img_flip'] = tuple(sample.get('img_flip', ())) + (angle,)
+        else:
+            out['img'] = np.ascontiguousarray(np.rot90(sample['img'], k=k, axes=(0, 1)))
+    out['gt_bboxes'] = rotate_bboxes(sample['gt_bboxes'], (h, w, 3), angle)
+    if sample.get('gt_masks') is not None:
+        if angle:
+            out['gt_masks'] = np.ascontiguousarray(np.rot90(sample['gt_masks'], k=k, axes=(1, 2)))
+    elif 'gt_polygons' in sample:
+        if angle:
+            out['mask_flips'] = tuple(sample.get('mask_flips', ())) + (angle,)
+    else:
+        raise KeyError("rotate_sample: the sample carries neither 'gt_masks' nor 'gt_polygons'")
+    out['gt_offsets'] = rotate_offsets(sample['gt_offsets'], angle)
+    out['rotate'], out['rotate_angle'] = True, angle
+    return out
+
+
+def _permute_masks(m, ops):
+    """Rasterised bitmaps [K,H,W] of a polygon sample under its recorded operations.  Flips alone: the mirrored copies as before;
+    a record with a rotation: composed to one element, one launch of loft_mask_d4_u8."""
+    if not _carries_rotation(ops):
+        for d in ops:                                       # flip_sample on a polygon sample: the bitmap is mirrored, as the
+            m = m.flip(2 if d == 'horizontal' else 1)       # reference's RandomFlip does after LoadAnnotations rasterised it
+        return m.contiguous()
+    elem = d4_compose(ops)
+    if elem == 0 or m.shape[0] == 0:
+        return m.contiguous()
+    from . import kernels as K
+    return K.mask_d4(m.contiguous(), elem)
+
+
 def _masks_of(s, dev):
     if 'gt_polygons' in s and s.get('gt_masks') is None:
         from . import kernels as K
         h, w = s['img'].shape[:2]
         m = K.poly2mask(s.get('gt_polygons_packed') or s['gt_polygons'], h, w, device=dev)
-        for d in s.get('mask_flips', ()):                   # flip_sample on a polygon sample: the bitmap is mirrored, as the
-            m = m.flip(2 if d == 'horizontal' else 1)       # reference's RandomFlip does after LoadAnnotations rasterised it
-        return m.contiguous()
+        return _permute_masks(m, s.get('mask_flips', ()))
     return torch.from_numpy(np.ascontiguousarray(s['gt_masks'], dtype=np.uint8)).to(dev)
+
+
+def _normalise_torch(imgs, rgb, flips, mean, std, to_rgb, dev):
+    """Normalize + bundle of a batch that carries no rotation: uint8 / float [n,H,W,3] -> fp32 [n,3,H,W]; ``flips``: per sample the
+    deferred RandomFlip directions."""
+    x = imgs.float()
+    if to_rgb and not all(rgb):
+        if any(rgb):
+            keep = torch.tensor(rgb, device=dev).view(-1, 1, 1, 1)
+            x = torch.where(keep, x, x.flip(-1))
+        else:
+            x = x.flip(-1)
+    for i, dirs in enumerate(flips):                                 # RandomFlip's image mirror, deferred by the loader
+        for d in dirs:
+            x[i] = x[i].flip(1 if d == 'horizontal' else 0)
+    x = (x - torch.tensor(mean, device=dev)) / torch.tensor(std, device=dev)
+    return x.permute(0, 3, 1, 2).contiguous()
 
 
 def to_device_batch(samples, device='cuda', mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375), to_rgb=True, staged=None):
@@ -163,33 +351,36 @@ def to_device_batch(samples, device='cuda', mean=(123.675, 116.28, 103.53), std=
     ``staged``: the images as one uint8 [n,H,W,3] host tensor (BonaiDataset's pinned staging ring; sample['img'] are views of it).
     masks go up once as uint8 [K,H,W] tensors -- or, when a sample carries ``gt_polygons`` (per instance a list of flat polygons: the
     annotation's ``masks`` entry, bonai.py:186-199) instead of ``gt_masks``, only the vertices go up and the bitmaps are rasterised on the
-    device (kernels.poly2mask = LoadAnnotations._poly2mask, loading.py:301-326): no K x 1024^2 host bitmaps, no upload."""
+    device (kernels.poly2mask = LoadAnnotations._poly2mask, loading.py:301-326): no K x 1024^2 host bitmaps, no upload.
+    A batch in which some sample's deferred record (``img_flip``) holds a rotation is normalised by kernels.image_prep_d4, and that
+    sample's rasterised bitmaps are permuted by kernels.mask_d4; a batch without a rotation takes the torch chain as before."""
     dev = torch.device(device)
     if staged is not None:       # uint8 [n, H, W, 3] holding the samples' images already (a pinned staging slot): one async upload
         imgs = staged.to(dev, non_blocking=True)
     else:
         imgs = torch.stack([torch.from_numpy(np.ascontiguousarray(s['img'])) for s in samples]).to(dev)
-    x = imgs.float()
     rgb = [bool(s.get('img_rgb', False)) for s in samples]         # decoded straight to RGB: Normalize's reversal already done
-    if to_rgb and not all(rgb):
-        if any(rgb):
-            keep = torch.tensor(rgb, device=dev).view(-1, 1, 1, 1)
-            x = torch.where(keep, x, x.flip(-1))
-        else:
-            x = x.flip(-1)
-    elif not to_rgb and any(rgb):
+    if not to_rgb and any(rgb):
         raise ValueError('samples decoded to RGB need to_rgb=True (the configured Normalize of bonai_instance.py:3-4)')
-    for i, s in enumerate(samples):                                  # RandomFlip's image mirror, deferred by the loader
-        for d in s.get('img_flip', ()):
-            x[i] = x[i].flip(1 if d == 'horizontal' else 0)
-    x = (x - torch.tensor(mean, device=dev)) / torch.tensor(std, device=dev)
-    img = x.permute(0, 3, 1, 2).contiguous()
+    if any(_carries_rotation(s.get('img_flip', ())) for s in samples):
+        # RandomRotate's image permutation, deferred by the loader: every sample's record of flips and rotations composed to one
+        # element, and the whole batch -- permutation, channel order, Normalize, HWC -> CHW -- in one launch
+        elems = [d4_compose(s.get('img_flip', ())) for s in samples]
+        if dev.type == 'cuda':
+            from . import kernels as K
+            img = K.image_prep_d4(imgs, elems, [r or not to_rgb for r in rgb], mean, std)
+        else:             # host tensors (device='cpu': the loader's CPU tests): the same permutation on the uint8 tiles, with numpy
+            imgs = torch.stack([torch.from_numpy(np.ascontiguousarray(d4_apply(t.numpy(), e))) for t, e in zip(imgs, elems)])
+            img = _normalise_torch(imgs, rgb, [()] * len(samples), mean, std, to_rgb, dev)
+    else:
+        img = _normalise_torch(imgs, rgb, [s.get('img_flip', ()) for s in samples], mean, std, to_rgb, dev)
     metas = []
     for s in samples:
         h, w = s['img'].shape[:2]
         metas.append(dict(filename=s.get('filename'), ori_shape=(h, w, 3), img_shape=(h, w, 3), pad_shape=(h, w, 3),
                           scale_factor=np.array([1., 1., 1., 1.], dtype=np.float32), flip=bool(s.get('flip', False)),
-                          flip_direction=s.get('flip_direction'),
+                          flip_direction=s.get('flip_direction'), rotate=bool(s.get('rotate', False)),
+                          rotate_angle=int(s.get('rotate_angle', 0)),
                           img_norm_cfg=dict(mean=np.array(mean, np.float32), std=np.array(std, np.float32), to_rgb=to_rgb)))
     if dev.type == 'cuda' and staged is not None:
         # the loader's path: every small array of the batch (boxes, labels, offsets, polygon vertices and their offset tables)
@@ -243,8 +434,6 @@ def _small_arrays_one_copy(samples, dev):
             continue
         h, w = s['img'].shape[:2]
         m = K.poly2mask_device(aux[i]['_xy'], aux[i]['_poff'], aux[i]['_ioff'], packs[i].n, h, w, packs[i].maxv)
-        for d in s.get('mask_flips', ()):
-            m = m.flip(2 if d == 'horizontal' else 1)
-        masks.append(m.contiguous())
+        masks.append(_permute_masks(m, s.get('mask_flips', ())))
     out['gt_masks'] = masks
     return out

@@ -16,6 +16,8 @@ What is mirrored, with the reference's semantics:
     of the same aspect-ratio group;
   * RandomFlip: probability ``flip_ratio`` per sample; a direction LIST is resolved once, when the pipeline is built
     (transforms.py:367-377: ``np.random.choice(direction)`` in ``__init__``) -- every flipped sample of a run uses that direction;
+  * RandomRotate (transforms.py:1837-2096), optional: probability ``rotate_ratio`` per sample, the angle drawn from
+    ``rotate_choice``; right angles on square tiles only, for the reason data.check_rotate_angles gives;
   * Resize / Pad: BONAI tiles are 1024 x 1024, the configured scale is (1024, 1024) with keep_ratio and the pad divisor 32, so both
     are identities; another tile size raises (the device path takes fixed-size batches).
 Image decoding uses PIL (cv2 / mmcv are not in this image); ``mmcv.imread`` returns BGR, so the RGB decode is reversed to BGR and
@@ -36,7 +38,7 @@ import os
 
 import numpy as np
 
-from .data import flip_sample, parse_bonai_annotations, to_device_batch
+from .data import check_rotate_angles, flip_sample, parse_bonai_annotations, rotate_sample, to_device_batch
 
 CLASSES = ('building',)
 
@@ -44,7 +46,8 @@ CLASSES = ('building',)
 class BonaiDataset:
     def __init__(self, ann_file, img_prefix='', classes=None, test_mode=False, filter_empty_gt=True, bbox_type='roof',
                  mask_type='roof', offset_coordinate='rectangle', resolution=0.6, ignore_buildings=True, flip_ratio=0.5,
-                 flip_direction=('horizontal', 'vertical'), img_scale=(1024, 1024), seed=0, host_rasteriser=None):
+                 flip_direction=('horizontal', 'vertical'), img_scale=(1024, 1024), seed=0, host_rasteriser=None,
+                 rotate_ratio=None, rotate_choice=(0, 90, 180, 270), rotate_first=False):
         ann_files = [ann_file] if isinstance(ann_file, str) else list(ann_file)
         prefixes = [img_prefix] * len(ann_files) if isinstance(img_prefix, str) else list(img_prefix)
         if len(prefixes) != len(ann_files):
@@ -64,6 +67,17 @@ class BonaiDataset:
             self.flip_direction = str(self.rng.choice(list(flip_direction)))
         if self.flip_direction not in ('horizontal', 'vertical'):
             raise ValueError(f"Invalid flipping direction '{self.flip_direction}'")
+        # RandomRotate (transforms.py:1837-2096): probability rotate_ratio per sample, then an angle drawn from rotate_choice;
+        # right angles on square tiles only (data.check_rotate_angles says why).  rotate_first: RandomRotate stands BEFORE
+        # RandomFlip in the pipeline -- the two do not commute, and each transform draws when it runs.
+        self.rotate_choice = check_rotate_angles(rotate_choice)
+        if rotate_ratio is not None and not 0 <= rotate_ratio <= 1:
+            raise ValueError(f'rotate_ratio is a probability, got {rotate_ratio}')
+        if rotate_ratio and not self.rotate_choice:
+            raise ValueError('rotate_choice is empty')
+        if rotate_ratio and self.img_scale[0] != self.img_scale[1] and any(a in (90, 270) for a in self.rotate_choice):
+            raise NotImplementedError(f'RandomRotate by 90 / 270 needs square tiles, img_scale is {self.img_scale}')
+        self.rotate_ratio, self.rotate_first = rotate_ratio, bool(rotate_first)
         self.data_infos, self.anns, self.cat_ids, self._ann_cache = [], [], None, {}
         for f, prefix in zip(ann_files, prefixes):
             self._load(f, prefix)
@@ -126,8 +140,9 @@ class BonaiDataset:
         rgb = np.asarray(Image.open(path).convert('RGB'))
         return np.ascontiguousarray(rgb[:, :, ::-1])                    # BGR, as mmcv.imread / cv2 deliver it
 
-    def prepare_train_img(self, idx, flip_draw=None, img_out=None, decode=True):
+    def prepare_train_img(self, idx, flip_draw=None, img_out=None, decode=True, rotate_angle='draw'):
         """One training sample.  flip_draw: the uniform draw that decides the flip (None: drawn here from self.rng).
+        rotate_angle: RandomRotate's decision -- an angle, None for "not rotated", 'draw': drawn here (resolve_all's order).
         decode=False (with img_out): everything but the pixels -- a decoder process fills img_out (decode_tile_into).
         img_out: optional uint8 [H, W, 3] array (a pinned staging slot of the prefetcher).  The decoder's RGB output then goes
         there with ONE copy and nothing else touches the pixels on the host: the sample says ``img_rgb`` (no BGR round trip:
@@ -170,25 +185,57 @@ class BonaiDataset:
                 sample['gt_polygons_packed'] = pk
         else:
             sample['gt_masks'] = np.stack([self.host_rasteriser(m, h, w) for m in ann['masks']])
-        if self.flip_ratio and (self.rng.rand() if flip_draw is None else flip_draw) < self.flip_ratio:
-            sample = flip_sample(sample, self.flip_direction, defer_image=img_out is not None)
+        for transform in ('rotate', 'flip') if self.rotate_first else ('flip', 'rotate'):
+            if transform == 'flip':
+                if self.flip_ratio and (self.rng.rand() if flip_draw is None else flip_draw) < self.flip_ratio:
+                    sample = flip_sample(sample, self.flip_direction, defer_image=img_out is not None)
+            elif self.rotate_ratio:
+                angle = self._draw_rotate() if isinstance(rotate_angle, str) else rotate_angle
+                if angle is not None:
+                    sample = rotate_sample(sample, angle, defer_image=img_out is not None)
         return sample
+
+    def _draw_rotate(self):
+        """RandomRotate's two draws (transforms.py:2017-2024): one uniform draw against rotate_ratio, and a ``choice`` draw only
+        when the sample rotates.  -> the angle, or None."""
+        if self.rng.rand() < self.rotate_ratio:
+            return int(self.rng.choice(self.rotate_choice))
+        return None
 
     def resolve(self, idx):
         """The random decisions of one training sample, in the reference's order: while the sample has no ground truth after
         parsing, another one of its aspect-ratio group (custom.py:170-191); then the flip draw (transforms.py:379-391).
         -> (index actually used, uniform draw for the flip)."""
+        return self._with_ground_truth(idx), self._flip_draw()
+
+    def _with_ground_truth(self, idx):
         while self.get_ann_info(idx)['bboxes'].shape[0] == 0:
             pool = np.where(self.flag == self.flag[idx])[0]
             idx = int(self.rng.choice(pool))
-        return idx, (float(self.rng.rand()) if self.flip_ratio else 1.0)
+        return idx
+
+    def _flip_draw(self):
+        return float(self.rng.rand()) if self.flip_ratio else 1.0
+
+    def resolve_all(self, idx):
+        """resolve() with RandomRotate's decision: -> (index actually used, uniform draw for the flip, angle or None).  The flip
+        draw and the rotation draws come in the order of the two transforms in the pipeline (``rotate_first``); without a
+        rotate_ratio no draw is added, and the stream of a seed is what resolve() gives."""
+        if not self.rotate_ratio:
+            return self.resolve(idx) + (None,)
+        idx = self._with_ground_truth(idx)
+        if self.rotate_first:
+            angle = self._draw_rotate()
+            return idx, self._flip_draw(), angle
+        draw = self._flip_draw()
+        return idx, draw, self._draw_rotate()
 
     def __getitem__(self, idx):
         if self.test_mode:
             info = self.data_infos[idx]
             return dict(img=self._read_image(info), filename=info['filename'])
-        idx, draw = self.resolve(idx)
-        return self.prepare_train_img(idx, flip_draw=draw)
+        idx, draw, angle = self.resolve_all(idx)
+        return self.prepare_train_img(idx, flip_draw=draw, rotate_angle=angle)
 
     # ------------------------------------------------------------------ batches
     def epoch_indices(self, epoch, samples_per_gpu, rank=0, world=1, shuffle=True, seed=0):
@@ -403,18 +450,19 @@ class _Prefetcher:
                         self.slot_free[k].synchronize()            # the upload that last read this slot has finished
                     buf = self.slots[k].numpy()
                     # every random decision in THIS thread, in the synchronous loader's order -- per sample: replacements of a
-                    # sample without ground truth (custom.py:188-191), then its flip draw -- so both loaders emit the same stream
+                    # sample without ground truth (custom.py:188-191), then its flip draw and RandomRotate's draws -- so both
+                    # loaders emit the same stream
                     futs, samples = [], []
                     h, w = buf.shape[1:3]
                     for i, j in enumerate(g):
-                        j, draw = self.ds.resolve(j)
+                        j, draw, angle = self.ds.resolve_all(j)
                         if self.processes:
                             info = self.ds.data_infos[j]
                             futs.append(pool.submit(decode_tile_into, os.path.join(info['_prefix'], info['filename']), self.shm.name,
                                                     k * self.slot_bytes + i * h * w * 3, h, w))
-                            samples.append(self.ds.prepare_train_img(j, draw, buf[i], decode=False))
+                            samples.append(self.ds.prepare_train_img(j, draw, buf[i], decode=False, rotate_angle=angle))
                         else:
-                            futs.append(pool.submit(self.ds.prepare_train_img, j, draw, buf[i]))
+                            futs.append(pool.submit(self.ds.prepare_train_img, j, draw, buf[i], True, angle))
                     if self.processes:
                         for f in futs:
                             err = f.result()

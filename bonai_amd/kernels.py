@@ -1586,6 +1586,39 @@ def poly2mask_device(xy, poff, ioff, n, H, W, maxv):
     return out
 
 
+# include/loft_hip.h LOFT_D4_*: an element of the square's symmetry group = optional transpose, then x-mirror, then y-mirror
+D4_TRANSPOSE, D4_MIRROR_X, D4_MIRROR_Y, D4_CHANNELS_KEPT = 1, 2, 4, 8
+
+
+def image_prep_d4(imgs_u8, elems, channels_kept, mean, std):
+    """loft_image_prep_d4: uint8 [n,H,W,3] device tensor -> normalised fp32 [n,3,H,W], sample i under the element ``elems[i]``
+    (D4_* bits), its channels reversed unless ``channels_kept[i]``.  One launch; (float(v) - mean[c]) / std[c] exactly."""
+    lib = L.load()
+    L.dev_check(imgs_u8)
+    if imgs_u8.dtype != torch.uint8 or imgs_u8.dim() != 4 or imgs_u8.shape[3] != 3 or not imgs_u8.is_contiguous():
+        raise L.LoftHipError(f'image_prep_d4 takes a contiguous uint8 [n,H,W,3] tensor, got {imgs_u8.dtype} {tuple(imgs_u8.shape)}')
+    n, H, W, _ = imgs_u8.shape
+    if len(elems) != n or len(channels_kept) != n or any(e & ~7 for e in elems):
+        raise L.LoftHipError('image_prep_d4: one element (0..7) and one channel flag per sample')
+    table = h2d([int(e) | (D4_CHANNELS_KEPT if k else 0) for e, k in zip(elems, channels_kept)], torch.int32, imgs_u8.device)
+    out = torch.empty(n, 3, H, W, dtype=torch.float32, device=imgs_u8.device)
+    L.check(lib.loft_image_prep_d4(L.ptr(imgs_u8), L.ptr(table), n, H, W, int(any(e & D4_TRANSPOSE for e in elems)),
+                                   mean[0], mean[1], mean[2], std[0], std[1], std[2], L.ptr(out), L.stream()), 'loft_image_prep_d4')
+    return out
+
+
+def mask_d4(masks_u8, elem):
+    """loft_mask_d4_u8: uint8 [K,H,W] device bitmaps -> the same bitmaps under one element (D4_* bits), a new tensor."""
+    lib = L.load()
+    L.dev_check(masks_u8)
+    if masks_u8.dtype != torch.uint8 or masks_u8.dim() != 3 or not masks_u8.is_contiguous():
+        raise L.LoftHipError(f'mask_d4 takes a contiguous uint8 [K,H,W] tensor, got {masks_u8.dtype} {tuple(masks_u8.shape)}')
+    K_, H, W = masks_u8.shape
+    out = torch.empty_like(masks_u8)
+    L.check(lib.loft_mask_d4_u8(L.ptr(masks_u8), K_, H, W, int(elem), L.ptr(out), L.stream()), 'loft_mask_d4_u8')
+    return out
+
+
 class PackedPolygons:
     """The host arrays loft_poly2mask reads (vertices fp64 [V,2], polygon offsets, instance offsets): built once per annotation
     (pack_polygons) and reusable -- the loader caches it per image instead of re-walking ~100 python lists every epoch."""

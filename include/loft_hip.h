@@ -616,6 +616,29 @@ int loft_mask_paste(const float* logits, const float* boxes, int N, int S, int i
  * masks uint8 [N,H,W], offsets fp32 [N,2] = (dx, dy) in pixels -> out[n, y, x] = masks[n, y + round(dy), x + round(dx)] (0 outside). */
 int loft_mask_translate(const uint8_t* masks, const float* offsets, int N, int H, int W, uint8_t* out, void* stream);
 
+/* ---- image-level augmentation on the device: the symmetries of the square (augment.hip) -----------
+ * RandomFlip (mmdet/datasets/pipelines/transforms.py:406-456) and RandomRotate by a right angle (:1837-2096), in any order and
+ * number, compose to one of eight elements: an optional transpose, THEN an optional x-mirror, THEN an optional y-mirror,
+ *     out[y][x] = in[r][c],  (r, c) = TRANSPOSE ? (x', y') : (y', x'),  x' = MIRROR_X ? W-1-x : x,  y' = MIRROR_Y ? H-1-y : y
+ * (a clockwise quarter turn, RandomRotate's 90, is TRANSPOSE | MIRROR_X).  Transposing elements go through an LDS tile: global
+ * memory is read and written along rows only.
+ * loft_image_prep_d4: Normalize + HWC -> CHW of a batch in one launch.  img uint8 [n,H,W,3]; elems: DEVICE int32 [n], per sample
+ *   an element, plus LOFT_D4_CHANNELS_KEPT when channel c of the output is channel c of the input (decoded to RGB already, or
+ *   to_rgb off) -- without it the channels are reversed (Normalize's to_rgb on a BGR decode); out fp32 [n,3,H,W] =
+ *   (float(v) - mean[c]) / std[c], an IEEE subtract and an IEEE divide.  any_transpose: nonzero when some entry of elems
+ *   transposes (the host cannot read the table).  Returns hipErrorInvalidValue without launching unless W % 4 == 0, and H == W
+ *   when any_transpose.
+ * loft_mask_d4_u8: masks uint8 [K,H,W] -> out uint8 [K,H,W] under ONE element (the bitmaps of a sample share the sample's);
+ *   out must not alias masks.  Same argument contract (W % 4 == 0; H == W for a transposing element). */
+#define LOFT_D4_TRANSPOSE 1
+#define LOFT_D4_MIRROR_X 2
+#define LOFT_D4_MIRROR_Y 4
+#define LOFT_D4_ELEMENT_MASK 7
+#define LOFT_D4_CHANNELS_KEPT 8
+int loft_image_prep_d4(const uint8_t* img, const int32_t* elems, int n, int H, int W, int any_transpose, float mean0, float mean1,
+                       float mean2, float std0, float std1, float std2, float* out, void* stream);
+int loft_mask_d4_u8(const uint8_t* masks, int K, int H, int W, int elem, uint8_t* out, void* stream);
+
 /* ---- sparse backward of the RPN head -------------------------------------------------------------
  * The RPN losses (anchor_head.py:429-497, rpn_head.py:56-80) read the head outputs only at the sampled anchors (<= 256 per
  * image of 261 888), so its backward runs on the selected pixels: level_ptrs/H/W (HOST arrays, n_levels <= 8) describe the

@@ -46,6 +46,19 @@ def optimizer_kwargs(cfg, model, options=(), verbose=False):
     return trainer_kwargs(cfg, model)
 
 
+def augment_kwargs(pipeline):
+    """BonaiDataset's augmentation arguments from the train pipeline: the RandomFlip entry (flip_ratio, direction) and the
+    RandomRotate entry (rotate_ratio, choice), and which of the two stands first -- they do not commute."""
+    names = [p.get('type') for p in pipeline]
+    flip = next((p for p in pipeline if p.get('type') == 'RandomFlip'), {})
+    kw = dict(flip_ratio=flip.get('flip_ratio', 0.0) or 0.0, flip_direction=flip.get('direction', 'horizontal'))
+    if 'RandomRotate' in names:
+        rot = pipeline[names.index('RandomRotate')]
+        kw.update(rotate_ratio=rot.get('rotate_ratio'), rotate_choice=rot.get('choice', (0, 90, 180, 270)),
+                  rotate_first='RandomFlip' in names and names.index('RandomRotate') < names.index('RandomFlip'))
+    return kw
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('config')
@@ -104,12 +117,11 @@ def main():
         files = [tcfg['ann_file']] if isinstance(tcfg['ann_file'], str) else list(tcfg['ann_file'])
         if files and all(os.path.exists(f) for f in files):
             from bonai_amd.dataset import BonaiDataset
-            flip = next((p for p in tcfg.get('pipeline', []) if p.get('type') == 'RandomFlip'), {})
             extra = {k: tcfg[k] for k in ('offset_coordinate', 'resolution', 'ignore_buildings', 'filter_empty_gt', 'classes')
                      if k in tcfg}                     # (bonai.py:18-35: the dataset's own keyword arguments)
             dataset = BonaiDataset(tcfg['ann_file'], tcfg.get('img_prefix', ''), bbox_type=tcfg.get('bbox_type', 'roof'),
-                                   mask_type=tcfg.get('mask_type', 'roof'), flip_ratio=flip.get('flip_ratio', 0.0) or 0.0,
-                                   flip_direction=flip.get('direction', 'horizontal'), seed=args.seed + rank, **extra)
+                                   mask_type=tcfg.get('mask_type', 'roof'), seed=args.seed + rank,
+                                   **augment_kwargs(tcfg.get('pipeline', [])), **extra)
             ipe = args.iters_per_epoch or max(1, len(dataset.epoch_indices(0, bs, rank, world)) // bs)
         elif rank == 0:
             print(f'dataset files of cfg.data.train not found ({files[:1]}...): synthetic tiles', flush=True)
