@@ -346,10 +346,11 @@ class BonaiDataset:
         except Exception:                                   # noqa
             pass
 
-    def test_batches(self, device='cuda'):
+    def test_batches(self, device='cuda', indices=None):
         """Test mode, samples_per_gpu = 1 (mmdet/apis/test.py:26 with the test pipeline of bonai_instance.py:18-31: one scale,
-        no flip): yields (idx, dict(img=[tensor 1x3xHxW], img_metas=[[meta]])) in dataset order."""
-        for i in range(len(self)):
+        no flip): yields (idx, dict(img=[tensor 1x3xHxW], img_metas=[[meta]])) in dataset order; ``indices``: only these images
+        (a shard of a validation pass), in the order given."""
+        for i in (range(len(self)) if indices is None else indices):
             info = self.data_infos[i]
             b = to_device_batch([dict(img=self._read_image(info), filename=info['filename'], gt_bboxes=np.zeros((0, 4), np.float32),
                                       gt_labels=np.zeros((0,), np.int64), gt_masks=np.zeros((0, 1, 1), np.uint8),

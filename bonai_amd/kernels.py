@@ -1739,6 +1739,49 @@ def mask_translate(masks, offsets):
     return out
 
 
+def mask_pair_counts(pm, gm, win, gbox=None, out=None):
+    """All prediction x ground-truth pixel intersections of one image, and every area, in one launch (loft_mask_pair_counts_u8).
+    pm uint8 [P,H,W], gm uint8 [G,H,W] (0/1, device); win [P,4] = (x0, y0, x1, y1) half-open windows, not pre-clipped: inter[p, g]
+    counts pm[p] & gm[g] inside win[p] clipped to the image; gbox [G,4] (optional) must contain every set pixel of gm[g] and only
+    saves reads.  win / gbox: int32 device tensors, or anything np.asarray takes (uploaded here).  ``out``: an int32 device buffer
+    of at least P*G + P + G elements to write into (several calls can share one buffer and one read-back).
+    -> (inter [P,G], area_p [P], area_g [G]) int32, views of one buffer laid out in that order.  P == 0 or G == 0: no launch;
+    inter is empty and the areas of the non-empty side are a plain sum (nothing to pair: not a path that is ever hot)."""
+    lib = L.load()
+    L.dev_check(pm, gm)
+    if pm.dim() != 3 or gm.dim() != 3 or pm.dtype != torch.uint8 or gm.dtype != torch.uint8 or pm.shape[1:] != gm.shape[1:]:
+        raise L.LoftHipError(f'mask_pair_counts: uint8 [P,H,W] and [G,H,W] expected, got {pm.dtype} {tuple(pm.shape)} and '
+                             f'{gm.dtype} {tuple(gm.shape)}')
+    pm, gm = pm.contiguous(), gm.contiguous()
+    P, G, (H, W) = pm.shape[0], gm.shape[0], pm.shape[1:]
+    dev = pm.device
+
+    def boxes(b, n, what):
+        if not isinstance(b, torch.Tensor):
+            b = torch.from_numpy(np.ascontiguousarray(np.asarray(b).reshape(-1, 4), dtype=np.int32))
+        b = b.to(device=dev, dtype=torch.int32).contiguous()
+        if tuple(b.shape) != (n, 4):
+            raise L.LoftHipError(f'mask_pair_counts: {what} [{n},4] expected, got {tuple(b.shape)}')
+        return b
+    win = boxes(win, P, 'win')
+    gbox = boxes(gbox, G, 'gbox') if gbox is not None else None
+    n = P * G + P + G
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=dev)
+    elif out.dtype != torch.int32 or out.dim() != 1 or out.numel() < n or not out.is_contiguous() or out.device != dev:
+        raise L.LoftHipError(f'mask_pair_counts: out must be a contiguous int32 device buffer of at least {n} elements')
+    inter, area_p, area_g = out[:P * G].view(P, G), out[P * G:P * G + P], out[P * G + P:n]
+    if P == 0 or G == 0:
+        if P:
+            area_p.copy_(pm.flatten(1).sum(1))
+        if G:
+            area_g.copy_(gm.flatten(1).sum(1))
+        return inter, area_p, area_g
+    L.check(lib.loft_mask_pair_counts_u8(L.ptr(pm), L.ptr(gm), L.ptr(win), L.ptr(gbox), P, G, H, W, L.ptr(inter), L.ptr(area_p),
+                                         L.ptr(area_g), L.stream()), 'loft_mask_pair_counts_u8')
+    return inter, area_p, area_g
+
+
 # ------------------------------------------------------------------ sparse RPN backward helpers
 
 def _sparse_levels(maps):

@@ -674,6 +674,12 @@ class LoftRoIHead(nn.Module):
         if rescale:
             bboxes = (bboxes.view(bboxes.size(0), -1, 4) / sf).view(bboxes.size(0), -1)
         det_bboxes, det_labels = self.multiclass_nms(bboxes, scores, cfg.score_thr, cfg.nms, cfg.max_per_img)
+        if cfg.get('paste_min_score') is not None and det_bboxes.shape[0]:
+            # opt-in (bonai_amd/validate.py sets it to the metric's score threshold): detections whose FINAL score is below it are
+            # dropped here, before the mask head, the full-image paste (1 MiB per detection on a 1024^2 tile) and the offset head
+            # spend anything on them.  Absent: every detection above test_cfg.rcnn.score_thr goes on, as the result pickle needs.
+            strong = det_bboxes[:, 4] >= float(cfg['paste_min_score'])
+            det_bboxes, det_labels = det_bboxes[strong], det_labels[strong]
         db = det_bboxes.cpu().numpy()
         dl = det_labels.cpu().numpy()
         bbox_results = [db[dl == i, :] for i in range(ncls)] if db.shape[0] else \

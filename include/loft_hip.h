@@ -615,6 +615,15 @@ int loft_mask_paste(const float* logits, const float* boxes, int N, int S, int i
  * footprint = roof translated by -offset; offsets are the third element of the result tuples of mmdet/apis/test.py:53-72).
  * masks uint8 [N,H,W], offsets fp32 [N,2] = (dx, dy) in pixels -> out[n, y, x] = masks[n, y + round(dy), x + round(dx)] (0 outside). */
 int loft_mask_translate(const uint8_t* masks, const float* offsets, int N, int H, int W, uint8_t* out, void* stream);
+/* loft_mask_pair_counts_u8 (eval_pairs.hip): every prediction x ground-truth pixel intersection of one image, and all areas, in one
+ * launch -- the numbers tools/bonai/bonai_evaluation.py:461-475 pairs buildings on.  pm uint8 [P,H,W], gm uint8 [G,H,W], values 0/1;
+ * win int32 [P,4] = (x0, y0, x1, y1) half-open, NOT pre-clipped (may be empty or wholly outside the image); gbox int32 [G,4] of the
+ * same form or NULL: gbox[g] must contain every set pixel of gm[g], and then only saves reads (results are the same with or without).
+ * -> inter int32 [P,G]: sum over win[p] clipped to the image of pm[p] & gm[g]; area_p int32 [P], area_g int32 [G]: full-image sums.
+ * Every output element is written (no zero fill needed), without atomics: exact and the same from run to run.  All DEVICE pointers.
+ * P == 0 or G == 0: returns 0 without a launch (nothing is written).  Limit: W <= 32752. */
+int loft_mask_pair_counts_u8(const uint8_t* pm, const uint8_t* gm, const int* win, const int* gbox, int P, int G, int H, int W,
+                             int* inter, int* area_p, int* area_g, void* stream);
 
 /* ---- image-level augmentation on the device: the symmetries of the square (augment.hip) -----------
  * RandomFlip (mmdet/datasets/pipelines/transforms.py:406-456) and RandomRotate by a right angle (:1837-2096), in any order and

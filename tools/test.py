@@ -19,34 +19,9 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-
-def run_dataset(model, ds, evaluate=False, eval_kw=None, log=print):
-    """-> (results as single_gpu_test returns them, per-image evaluation records or None)."""
-    from bonai_amd import evaluation as E
-    roi = model.roi_head
-    roi.test_cfg['keep_device_masks'] = True
-    # simple_test encodes the pasted device bitmaps as RLE itself (one pass): without this it also copied every detection's
-    # full-image bool mask to the host (up to 100 x 1 MiB per tile) for a result this loop then threw away (ADVICE round 4)
-    roi.test_cfg['rle_masks'] = True
-    results, records = [], ([] if evaluate else None)
-    for i, data in ds.test_batches():
-        with torch.no_grad():
-            bbox_res, segm, off_res = model(return_loss=False, rescale=True, **data)
-        n_det = sum(b.shape[0] for b in bbox_res)
-        pasted = roi.last_device_masks if n_det else None
-        results.append((bbox_res, segm, off_res))
-        if evaluate:
-            h, w = data['img_metas'][0][0]['ori_shape'][:2]
-            pm = pasted if pasted is not None else torch.zeros(0, h, w, dtype=torch.uint8, device=data['img'][0].device)
-            boxes = roi.last_dets if pasted is not None else np.zeros((0, 5), np.float32)
-            offs = np.asarray(off_res, np.float32).reshape(-1, 2) if pasted is not None else np.zeros((0, 2), np.float32)
-            records.append(E.evaluate_image(pm, boxes, offs, ds.get_ann_info(i), **(eval_kw or {})))
-        if (i + 1) % 50 == 0 or i + 1 == len(ds):
-            log(f'[{i + 1}/{len(ds)}]')
-    return results, records
+from bonai_amd.validate import run_dataset  # noqa: E402,F401  (the loop lives in the library: the trainer validates with it too)
 
 
 def main():

@@ -2,14 +2,21 @@
 """Entry point with the argv surface of the reference's tools/train.py:25-64 for the LOFT hot path.
 
     python tools/train.py configs/loft_foa/loft_foa_r50_fpn_2x_bonai.py [--work-dir D] [--launcher pytorch]
-                          [--options k=v ...] [--iters N] [--synthetic]
+                          [--options k=v ...] [--iters N] [--synthetic] [--no-validate] [--val-ann-file F --val-img-prefix D]
 
 Data: when the annotation files of ``cfg.data.train`` exist, batches come from them (bonai_amd/dataset.py: the reference's
 BONAI dataset + train pipeline semantics, polygons rasterised and images normalised on the device), sharded over the ranks like
 DistributedGroupSampler; otherwise -- offline, as in this image -- or with ``--synthetic``, seeded 1024x1024 tiles with the
 reference's batch-dict keys.  Logging mirrors TextLoggerHook's key set (default_runtime.py:3-8).
+
+Validation (the reference's EvalHook, apis/train.py:113-126): when the annotation files of ``cfg.data.val`` -- or ``--val-ann-file``
+-- exist, every ``cfg.evaluation.interval``-th epoch ends with a pass over them (bonai_amd/validate.py: roof / footprint F1 and
+offset aEPE / aAE, sharded over the ranks), an ``Epoch(val)`` line and a line in WORK_DIR/val.log.json; ``evaluation.save_best``
+keeps best.pth.  When batches come from annotation files, ``checkpoint_config.interval`` writes epoch_{E}.pth (a synthetic stream
+has no epochs of its own: latest.pth only).  Validation runs uncaptured and is refused together with ``--graph``.
 """
 import argparse
+import json
 import os
 import sys
 import time
@@ -75,6 +82,9 @@ def main():
     ap.add_argument('--synthetic', action='store_true', help='seeded synthetic tiles even when the dataset files are present')
     ap.add_argument('--prefetch', type=int, default=2, help='dataset batches decoded / uploaded ahead of the step (0: synchronous loader)')
     ap.add_argument('--graph', action='store_true', help='backbone + neck forward / backward as two hipGraphs (bonai_amd/graphs.py)')
+    ap.add_argument('--no-validate', action='store_true', help='no validation pass at epoch ends (tools/train.py:36-39 of the reference)')
+    ap.add_argument('--val-ann-file', help='validation annotation file (default: cfg.data.val.ann_file)')
+    ap.add_argument('--val-img-prefix', help='validation tile directory (default: cfg.data.val.img_prefix)')
     args = ap.parse_args()
     from bonai_amd.config import Config
     from bonai_amd.engine import Trainer, step_lr
@@ -96,6 +106,19 @@ def main():
         L.set_act16(torch.float16)
     if args.pretrained:
         cfg.model['pretrained'] = args.pretrained
+    # validation: only when its annotation files are there (no existing invocation has them: nothing new runs then)
+    vcfg = (cfg.data.get('val') if cfg.get('data') else None) or {}
+    val_ann = args.val_ann_file or vcfg.get('ann_file')
+    val_files = [val_ann] if isinstance(val_ann, str) else list(val_ann or [])
+    validate = not args.no_validate and bool(val_files) and all(os.path.exists(f) for f in val_files)
+    ev = None
+    if validate:
+        from bonai_amd.validate import parse_evaluation
+        ev = parse_evaluation(cfg.get('evaluation'), log=(lambda m: print(m, flush=True)) if rank == 0 else (lambda m: None))
+        if args.graph:
+            raise SystemExit('--graph together with validation is refused: the validation pass runs uncaptured between two steps, and '
+                             'that a captured backbone + neck step replays correctly after it has not been shown on the device.  '
+                             'Give --no-validate, or train without --graph.')
     model = build_detector(cfg.model, train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg).cuda().train()
     if args.load_from:
         load_checkpoint(model, args.load_from, strict=False)
@@ -117,7 +140,7 @@ def main():
         files = [tcfg['ann_file']] if isinstance(tcfg['ann_file'], str) else list(tcfg['ann_file'])
         if files and all(os.path.exists(f) for f in files):
             from bonai_amd.dataset import BonaiDataset
-            extra = {k: tcfg[k] for k in ('offset_coordinate', 'resolution', 'ignore_buildings', 'filter_empty_gt', 'classes')
+            extra = {k: tcfg[k] for k in ('offset_coordinate', 'resolution', 'ignore_buildings', 'filter_empty_gt', 'classes', 'img_scale')
                      if k in tcfg}                     # (bonai.py:18-35: the dataset's own keyword arguments)
             dataset = BonaiDataset(tcfg['ann_file'], tcfg.get('img_prefix', ''), bbox_type=tcfg.get('bbox_type', 'roof'),
                                    mask_type=tcfg.get('mask_type', 'roof'), seed=args.seed + rank,
@@ -139,6 +162,43 @@ def main():
                     return
                 yield it, data
                 it += 1
+    validator = None
+    if validate:
+        from bonai_amd.dataset import BonaiDataset
+        from bonai_amd.validate import Validator, is_better, val_line
+        vextra = {k: vcfg[k] for k in ('bbox_type', 'mask_type', 'offset_coordinate', 'resolution', 'classes') if k in vcfg}
+        vprefix = args.val_img_prefix if args.val_img_prefix is not None else vcfg.get('img_prefix', '')
+        validator = Validator(model, BonaiDataset(val_ann, vprefix, test_mode=True, **vextra), score_thr=ev['score_thr'],
+                              min_area=ev['min_area'], iou_thr=ev['iou_thr'], rank=rank, world=world, num=ev['num'])
+    ckpt_every = int((cfg.get('checkpoint_config') or {}).get('interval', 1) or 0)
+    best = dict(value=None, epoch=None)
+
+    def save(name, it_done, epoch, **meta):
+        os.makedirs(args.work_dir, exist_ok=True)
+        save_checkpoint(model, os.path.join(args.work_dir, name), optimizer_state=tr.optimizer_state_dict(),
+                        meta=dict(config=cfg.filename, iter=it_done, epoch=epoch, **meta))
+
+    def epoch_end(it_done, epoch):
+        """After the last iteration of epoch ``epoch`` (1-based): validation, best checkpoint, epoch checkpoint."""
+        if validator is not None and epoch % ev['interval'] == 0:
+            summary = validator.run()                      # every rank runs its shard; all hold the same totals afterwards
+            if rank == 0:
+                print(val_line(epoch, validator.num, summary), flush=True)
+                rec = dict(mode='val', epoch=epoch, iter=it_done, **summary)
+                if ev['save_best']:
+                    name, key = ev['save_best'].split('.', 1)
+                    if is_better(ev['save_best'], summary[name][key], best['value']):
+                        best.update(value=summary[name][key], epoch=epoch)
+                        if args.work_dir:
+                            save('best.pth', it_done, epoch, best={ev['save_best']: best['value']})
+                    rec['best'] = dict(key=ev['save_best'], value=best['value'], epoch=best['epoch'])
+                if args.work_dir:
+                    os.makedirs(args.work_dir, exist_ok=True)
+                    with open(os.path.join(args.work_dir, 'val.log.json'), 'a') as f:
+                        f.write(json.dumps(rec) + '\n')
+        if dataset is not None and args.work_dir and rank == 0 and ckpt_every > 0 and epoch % ckpt_every == 0:
+            save(f'epoch_{epoch}.pth', it_done, epoch)
+
     t0 = time.time()
     for it, data in stream():
         out = tr.train_step(data, lr=step_lr(cfg.optimizer.lr, it, it // ipe, **sched))
@@ -149,6 +209,8 @@ def main():
                 ls = tr.loss_scale_state()
                 lv += f", loss_scale: {ls['scale']:g}, skipped: {ls['skipped']}, grad_norm: {ls['grad_norm']:.4f}"
             print(f'Epoch [{it // ipe + 1}][{it % ipe + 1}/{ipe}] time: {(time.time() - t0) / (it - start_iter + 1):.3f}, {lv}', flush=True)
+        if (it + 1) % ipe == 0 and (validator is not None or dataset is not None):
+            epoch_end(it + 1, (it + 1) // ipe)
     if args.work_dir and rank == 0:
         os.makedirs(args.work_dir, exist_ok=True)
         save_checkpoint(model, os.path.join(args.work_dir, 'latest.pth'), optimizer_state=tr.optimizer_state_dict(),
