@@ -15,6 +15,7 @@
 //                    (mmdet/core/mask/mask_target.py:33-62, structures.py:261-291) -- replaces the
 //                    GPU->CPU->GPU round trip
 #include "loft_common.h"
+#include "box_codec.h"
 #include <algorithm>
 #include "../../include/loft_hip.h"
 
@@ -155,26 +156,7 @@ LOFT_EXPORT int loft_iou_assign(const float* boxes, const int* nbox, int Nmax, c
 }
 
 // ---- DeltaXYWHBBoxCoder ---------------------------------------------------------------------
-__device__ __forceinline__ float4 decode_box(const float4 r, float d0, float d1, float d2, float d3, const float* means,
-                                             const float* stds, float max_ratio, float max_h, float max_w) {
-    const float dx = d0 * stds[0] + means[0], dy = d1 * stds[1] + means[1];
-    float dw = d2 * stds[2] + means[2], dh = d3 * stds[3] + means[3];
-    dw = fminf(fmaxf(dw, -max_ratio), max_ratio);
-    dh = fminf(fmaxf(dh, -max_ratio), max_ratio);
-    const float px = (r.x + r.z) * 0.5f, py = (r.y + r.w) * 0.5f;
-    const float pw = r.z - r.x, ph = r.w - r.y;
-    const float gw = pw * expf(dw), gh = ph * expf(dh);
-    const float gx = px + pw * dx, gy = py + ph * dy;
-    float4 o;
-    o.x = gx - gw * 0.5f; o.y = gy - gh * 0.5f; o.z = gx + gw * 0.5f; o.w = gy + gh * 0.5f;
-    if (max_w > 0.f) {
-        o.x = fminf(fmaxf(o.x, 0.f), max_w); o.z = fminf(fmaxf(o.z, 0.f), max_w);
-        o.y = fminf(fmaxf(o.y, 0.f), max_h); o.w = fminf(fmaxf(o.w, 0.f), max_h);
-    }
-    return o;
-}
-
-struct Coder4 { float means[4], stds[4]; };
+// (decode_box and Coder4: box_codec.h, shared with tta.hip)
 
 __global__ void delta2bbox_kernel(const float* __restrict__ rois, const float* __restrict__ deltas, long n, Coder4 c,
                                   float max_ratio, float max_h, float max_w, float* __restrict__ out) {
@@ -483,18 +465,8 @@ __global__ void foa_fuse_decode_kernel(const float* __restrict__ pred, const flo
                                        float std_y, float max_h, float max_w, float* __restrict__ out) {
     const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float b0x = pred[(0 * n + i) * 2], b0y = pred[(0 * n + i) * 2 + 1];
-    const float b1x = pred[(1 * n + i) * 2], b1y = pred[(1 * n + i) * 2 + 1];
-    const float b2x = pred[(2 * n + i) * 2], b2y = pred[(2 * n + i) * 2 + 1];
-    const float b3x = pred[(3 * n + i) * 2], b3y = pred[(3 * n + i) * 2 + 1];
-    const float vx = fmaxf(fmaxf(fabsf(b0x), fabsf(b1y)), fmaxf(fabsf(b2x), fabsf(b3y)));
-    const float vy = fmaxf(fmaxf(fabsf(b0y), fabsf(b1x)), fmaxf(fabsf(b2y), fabsf(b3x)));
-    const float fx = vx * (b0x > 0.f ? 1.f : -1.f), fy = vy * (b0y > 0.f ? 1.f : -1.f);
-    const float4 r = reinterpret_cast<const float4*>(boxes)[i];
-    float gx = (r.z - r.x) * (fx * std_x), gy = (r.w - r.y) * (fy * std_y);
-    gx = fminf(fmaxf(gx, -max_w), max_w);
-    gy = fminf(fmaxf(gy, -max_h), max_h);
-    out[2 * i] = gx; out[2 * i + 1] = gy;
+    const float2 g = foa_fuse_decode_one(pred, n, i, reinterpret_cast<const float4*>(boxes)[i], std_x, std_y, max_h, max_w);
+    out[2 * i] = g.x; out[2 * i + 1] = g.y;
 }
 LOFT_EXPORT int loft_foa_fuse_decode(const float* pred, const float* boxes, int64_t n, float std_x, float std_y, float max_h,
                                      float max_w, float* out, void* stream) {
@@ -536,15 +508,9 @@ __global__ void offset_decode_kernel(const float* __restrict__ pred, const float
                                      float* __restrict__ out) {
     const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
     if (i >= n) return;
-    float d0, d1;
-    if (reg_num == 2) { d0 = pred[2 * i]; d1 = pred[2 * i + 1]; }
-    else { d0 = pred[3 * i]; d1 = atan2f(pred[3 * i + 2], pred[3 * i + 1]); }
-    const float4 r = reinterpret_cast<const float4*>(boxes)[i];
-    float gx = (r.z - r.x) * (d0 * std_x + mean_x), gy = (r.w - r.y) * (d1 * std_y + mean_y);
-    gx = fminf(fmaxf(gx, -max_w), max_w);
-    gy = fminf(fmaxf(gy, -max_h), max_h);
-    if (polar) { const float l = gx, a = gy; gx = l * cosf(a); gy = l * sinf(a); }
-    out[2 * i] = gx; out[2 * i + 1] = gy;
+    const float2 g = offset_decode_one(pred, i, reinterpret_cast<const float4*>(boxes)[i], mean_x, mean_y, std_x, std_y, max_h, max_w,
+                                       reg_num, polar);
+    out[2 * i] = g.x; out[2 * i + 1] = g.y;
 }
 LOFT_EXPORT int loft_offset_decode(const float* pred, const float* boxes, int64_t n, float mean_x, float mean_y, float std_x,
                                    float std_y, float max_h, float max_w, int reg_num, int polar, float* out, void* stream) {
@@ -741,31 +707,15 @@ __global__ void mask_paste_kernel(const float* __restrict__ logits, const float*
     const int y = blockIdx.y, n = blockIdx.z;
     if (x >= img_w) return;
     const float4 b = reinterpret_cast<const float4*>(boxes)[n];
-    // reference CPU path (skip_empty=True, one instance per chunk): only the tight integer region around the box
-    if ((float)x < fmaxf(floorf(b.x) - 1.f, 0.f) || (float)x >= fminf(ceilf(b.z) + 1.f, (float)img_w) ||
-        (float)y < fmaxf(floorf(b.y) - 1.f, 0.f) || (float)y >= fminf(ceilf(b.w) + 1.f, (float)img_h)) {
+    if (paste_outside(x, y, b, img_h, img_w)) {
         out[((long)n * img_h + y) * img_w + x] = 0;
         return;
     }
-    float gx = ((float)x + 0.5f - b.x) / (b.z - b.x) * 2.f - 1.f;
-    float gy = ((float)y + 0.5f - b.y) / (b.w - b.y) * 2.f - 1.f;
-    if (isinf(gx)) gx = 0.f;
-    if (isinf(gy)) gy = 0.f;
-    // grid_sample, align_corners=False: source coordinate = ((g + 1) * S - 1) / 2
-    const float sx = ((gx + 1.f) * (float)S - 1.f) * 0.5f, sy = ((gy + 1.f) * (float)S - 1.f) * 0.5f;
-    float v = 0.f;
-    if (sx > -1.f && sx < (float)S && sy > -1.f && sy < (float)S) {
-        const float fx = floorf(sx), fy = floorf(sy);
-        const int x0 = (int)fx, y0 = (int)fy;
-        const float lx = sx - fx, ly = sy - fy;
-        const float* m = logits + (long)n * S * S;
-        auto at = [&](int yy, int xx) -> float {
-            if (yy < 0 || yy >= S || xx < 0 || xx >= S) return 0.f;
-            return 1.f / (1.f + expf(-m[yy * S + xx]));
-        };
-        v = at(y0, x0) * (1.f - ly) * (1.f - lx) + at(y0, x0 + 1) * (1.f - ly) * lx + at(y0 + 1, x0) * ly * (1.f - lx) +
-            at(y0 + 1, x0 + 1) * ly * lx;
-    }
+    const float* m = logits + (long)n * S * S;
+    const float v = paste_sample(x, y, b, S, [&](int yy, int xx) -> float {
+        if (yy < 0 || yy >= S || xx < 0 || xx >= S) return 0.f;
+        return paste_sigmoid(m[yy * S + xx]);
+    });
     out[((long)n * img_h + y) * img_w + x] = v >= thr ? 1 : 0;
 }
 LOFT_EXPORT int loft_mask_paste(const float* logits, const float* boxes, int N, int S, int img_h, int img_w, float thr,

@@ -47,7 +47,7 @@ class BonaiDataset:
     def __init__(self, ann_file, img_prefix='', classes=None, test_mode=False, filter_empty_gt=True, bbox_type='roof',
                  mask_type='roof', offset_coordinate='rectangle', resolution=0.6, ignore_buildings=True, flip_ratio=0.5,
                  flip_direction=('horizontal', 'vertical'), img_scale=(1024, 1024), seed=0, host_rasteriser=None,
-                 rotate_ratio=None, rotate_choice=(0, 90, 180, 270), rotate_first=False):
+                 rotate_ratio=None, rotate_choice=(0, 90, 180, 270), rotate_first=False, test_views=None):
         ann_files = [ann_file] if isinstance(ann_file, str) else list(ann_file)
         prefixes = [img_prefix] * len(ann_files) if isinstance(img_prefix, str) else list(img_prefix)
         if len(prefixes) != len(ann_files):
@@ -78,6 +78,16 @@ class BonaiDataset:
         if rotate_ratio and self.img_scale[0] != self.img_scale[1] and any(a in (90, 270) for a in self.rotate_choice):
             raise NotImplementedError(f'RandomRotate by 90 / 270 needs square tiles, img_scale is {self.img_scale}')
         self.rotate_ratio, self.rotate_first = rotate_ratio, bool(rotate_first)
+        # test-time augmentation (bonai_amd/tta.py): the views test_batches yields per tile -- None / [None]: the tile alone, as before
+        self.test_views = list(test_views) if test_views else None
+        if self.test_views is not None:
+            from .tta import make_views
+            if self.test_views[0] is not None:
+                raise ValueError(f'test_views {self.test_views}: the list starts with None, the tile itself')
+            make_views([v for v in self.test_views[1:] if isinstance(v, str)], [v for v in self.test_views[1:] if not isinstance(v, str)],
+                       (self.img_scale[1], self.img_scale[0]))
+            if len(self.test_views) == 1:
+                self.test_views = None
         self.data_infos, self.anns, self.cat_ids, self._ann_cache = [], [], None, {}
         for f, prefix in zip(ann_files, prefixes):
             self._load(f, prefix)
@@ -352,10 +362,33 @@ class BonaiDataset:
         (a shard of a validation pass), in the order given."""
         for i in (range(len(self)) if indices is None else indices):
             info = self.data_infos[i]
+            if self.test_views is not None:
+                yield i, self._view_batch(info, device)
+                continue
             b = to_device_batch([dict(img=self._read_image(info), filename=info['filename'], gt_bboxes=np.zeros((0, 4), np.float32),
                                       gt_labels=np.zeros((0,), np.int64), gt_masks=np.zeros((0, 1, 1), np.uint8),
                                       gt_offsets=np.zeros((0, 2), np.float32))], device=device)
             yield i, dict(img=[b['img']], img_metas=[b['img_metas']])
+
+    def _view_batch(self, info, device, mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375)):
+        """One tile under ``test_views``: the tile goes up once as uint8 and ALL V view images come from one image_prep_d4 launch
+        (which reads a dense uint8 [V,H,W,3]: the uploaded tile repeated on the device).
+        -> dict(img=[V tensors 1x3xHxW], img_metas=[[meta_v]]), the shape of the reference's MultiScaleFlipAug output."""
+        import torch
+        from . import kernels as K
+        from .tta import view_element, view_meta
+        img = self._read_image(info)
+        h, w = img.shape[:2]
+        elems = [view_element(v) for v in self.test_views]
+        if h != w and any(e & K.D4_TRANSPOSE for e in elems):
+            raise NotImplementedError(f'a test view rotated by 90 / 270 needs a square tile, got {w}x{h}')
+        V = len(elems)
+        u8 = torch.from_numpy(np.ascontiguousarray(img)).to(device)
+        views = K.image_prep_d4(u8[None].expand(V, h, w, 3).contiguous(), elems, [False] * V, mean, std)
+        meta = dict(filename=info['filename'], ori_shape=(h, w, 3), img_shape=(h, w, 3), pad_shape=(h, w, 3),
+                    scale_factor=np.array([1., 1., 1., 1.], dtype=np.float32), flip=False, flip_direction=None, rotate=False,
+                    rotate_angle=0, img_norm_cfg=dict(mean=np.array(mean, np.float32), std=np.array(std, np.float32), to_rgb=True))
+        return dict(img=[views[v:v + 1] for v in range(V)], img_metas=[[view_meta(meta, op)] for op in self.test_views])
 
 
 _SHM_CACHE = {}

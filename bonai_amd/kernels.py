@@ -1724,6 +1724,92 @@ def mask_paste(logits, boxes, img_h, img_w, thr=0.5):
     return out
 
 
+# ------------------------------------------------------------------ test-time augmentation (csrc/tta.hip)
+
+NMS_MAX_SEGMENT = 32768      # nms.hip NMS_MAX_WORDS_PER_LANE: the longest segment loft_nms_segmented_* takes (64 * 64 * 8 boxes)
+TTA_MAX_VIEWS = 8            # tta.hip TTA_MAX_VIEWS: the square has eight symmetries
+
+
+def tta_view_table(elems, device):
+    """The views' D4_* elements as the small device table (int32 [V]) every tta_* kernel reads."""
+    elems = [int(e) for e in elems]
+    if not 1 <= len(elems) <= TTA_MAX_VIEWS or any(e & ~7 for e in elems):
+        raise L.LoftHipError(f'test-time augmentation takes 1..{TTA_MAX_VIEWS} views, each an element 0..7; got {elems}')
+    return h2d(elems, torch.int32, device)
+
+
+def _tta_check_shape(elems, img_h, img_w):
+    if img_h != img_w and any(int(e) & D4_TRANSPOSE for e in elems):
+        raise L.LoftHipError(f'a transposing view needs a square tile, got {img_w}x{img_h}')
+
+
+def tta_view_rois(boxes, views, V, img_h, img_w):
+    """boxes [n,>=4] in the original frame -> RoIs [V*n,5] view-major: bbox_mapping + bbox2roi for all views, one launch."""
+    lib = L.load()
+    L.dev_check(boxes, views)
+    boxes = boxes[:, :4].float().contiguous()
+    n = boxes.shape[0]
+    rois = torch.empty(V * n, 5, dtype=torch.float32, device=boxes.device)
+    L.check(lib.loft_tta_view_rois(L.ptr(boxes), n, L.ptr(views), V, int(img_h), int(img_w), L.ptr(rois), L.stream()), 'loft_tta_view_rois')
+    return rois
+
+
+def tta_gather_proposals(props, counts, views, img_h, img_w):
+    """(props [V,P,5], counts int64 [V]) of the views -> compact [sum(counts),5] mapped back to the original frame, scores kept.
+    The row offsets come from the counts on the device; the one host read is their total."""
+    lib = L.load()
+    L.dev_check(props, counts, views)
+    props, counts = props.float().contiguous(), counts.to(torch.int64).contiguous()
+    V, P = props.shape[0], props.shape[1]
+    total = int(counts.clamp(0, P).sum().item())
+    out = torch.empty(total, 5, dtype=torch.float32, device=props.device)
+    L.check(lib.loft_tta_gather_proposals(L.ptr(props), L.ptr(counts), V, P, L.ptr(views), int(img_h), int(img_w), total, L.ptr(out),
+                                          L.stream()), 'loft_tta_gather_proposals')
+    return out
+
+
+def tta_merge_bboxes(rois, bbox_pred, cls_score, V, views, img_h, img_w, means, stds, wh_ratio_clip=16 / 1000):
+    """aug_test_bboxes' per-view softmax + delta2bbox (clipped to the view's shape) + map back, and merge_aug_bboxes' mean over the
+    views: rois [V*n,5], bbox_pred [V*n,4C | 4], cls_score [V*n,C+1] -> (bboxes [n,4C | 4], scores [n,C+1])."""
+    lib = L.load()
+    L.dev_check(rois, bbox_pred, cls_score, views)
+    rois, bbox_pred, cls_score = rois.float().contiguous(), bbox_pred.float().contiguous(), cls_score.float().contiguous()
+    n, C, Cb = rois.shape[0] // V, cls_score.shape[1] - 1, bbox_pred.shape[1] // 4
+    bboxes = torch.empty(n, 4 * Cb, dtype=torch.float32, device=rois.device)
+    scores = torch.empty(n, C + 1, dtype=torch.float32, device=rois.device)
+    L.check(lib.loft_tta_merge_bboxes(L.ptr(rois), L.ptr(bbox_pred), L.ptr(cls_score), n, V, C, Cb, L.ptr(views), int(img_h), int(img_w),
+                                      L.arr(c_float, list(means)), L.arr(c_float, list(stds)), wh_ratio_clip, L.ptr(bboxes),
+                                      L.ptr(scores), L.stream()), 'loft_tta_merge_bboxes')
+    return bboxes, scores
+
+
+def tta_merge_offsets(pred, rois, V, views, means=(0., 0.), stds=(0.5, 0.5), max_shape=(1024, 1024), foa=True, polar=False):
+    """One run of the offset head over the view-major RoIs [V*n,5] -> merged offsets [n,2] in the original frame: per view
+    foa_fuse_decode (``foa``: pred [4*V*n,2] branch-major) or offset_decode (pred [V*n,2|3]), the vector mapped back, mean over views."""
+    lib = L.load()
+    L.dev_check(pred, rois, views)
+    pred, rois = pred.float().contiguous(), rois.float().contiguous()
+    n = rois.shape[0] // V
+    out = torch.empty(n, 2, dtype=torch.float32, device=rois.device)
+    L.check(lib.loft_tta_merge_offsets(L.ptr(pred), L.ptr(rois), n, V, 0 if foa else int(pred.shape[1]), L.ptr(views), means[0], means[1],
+                                       stds[0], stds[1], max_shape[0], max_shape[1], 1 if polar else 0, L.ptr(out), L.stream()),
+            'loft_tta_merge_offsets')
+    return out
+
+
+def mask_paste_views(logits, boxes, views, img_h, img_w, thr=0.5):
+    """logits fp32 [V,N,S,S] (class selected) of the views, boxes [N,4] in the original frame -> uint8 [N,img_h,img_w]: mask_paste of
+    the mean over views of sigmoid(logit), each view read through its inverse permutation of the grid."""
+    lib = L.load()
+    L.dev_check(logits, boxes, views)
+    logits, boxes = logits.float().contiguous(), boxes[:, :4].float().contiguous()
+    V, N, S = logits.shape[0], logits.shape[1], logits.shape[-1]
+    out = torch.empty(N, img_h, img_w, dtype=torch.uint8, device=logits.device)
+    L.check(lib.loft_mask_paste_views(L.ptr(logits), L.ptr(boxes), N, V, S, L.ptr(views), int(img_h), int(img_w), thr, L.ptr(out),
+                                      L.stream()), 'loft_mask_paste_views')
+    return out
+
+
 def mask_translate(masks, offsets):
     """Footprints from roofs: masks uint8/bool [N,H,W], offsets fp32 [N,2] = (dx, dy) footprint -> roof (the model's offset
     output) -> uint8 [N,H,W] with out[n, y, x] = masks[n, y + round(dy), x + round(dx)], zero outside the image."""

@@ -8,6 +8,7 @@ device->host copy.
 """
 from collections import OrderedDict
 
+import numpy as np
 import torch
 import torch.distributed as dist
 from torch import nn
@@ -141,7 +142,7 @@ class LOFT(nn.Module):
 
     def forward_test(self, imgs, img_metas, **kwargs):
         if len(imgs) != 1:
-            raise NotImplementedError('test-time augmentation (configs/loft_foa: flip=False, one scale)')
+            return self.aug_test(imgs, img_metas, **kwargs)
         assert imgs[0].size(0) == 1, 'samples_per_gpu must be 1 at test time (base.py:142-143)'
         return self.simple_test(imgs[0], img_metas[0], **kwargs)
 
@@ -149,6 +150,25 @@ class LOFT(nn.Module):
         x = self.extract_feat(img)
         proposal_list = self.rpn_head.simple_test_rpn(x, img_metas) if proposals is None else proposals
         return self.roi_head.simple_test(x, proposal_list, img_metas, rescale=rescale)
+
+    @torch.no_grad()
+    def aug_test(self, imgs, img_metas, rescale=False):
+        """two_stage.py:201-211 for the views of ONE tile (bonai_amd/tta.py): imgs = V tensors [1,3,H,W], img_metas = [[meta_v]], the
+        first view the tile itself.  The backbone, the RPN head and each RoI head run once on the V views as a batch of V; the
+        merges are bonai_amd/csrc/tta.hip.  -> simple_test's 3-tuple (the reference's aug_test drops the offsets: an extension)."""
+        from ..tta import meta_element
+        if len(imgs) != len(img_metas) or any(im.size(0) != 1 or len(m) != 1 for im, m in zip(imgs, img_metas)):
+            raise ValueError('aug_test takes one tile: V view images [1,3,H,W] and img_metas = [[meta_v]] (samples_per_gpu = 1)')
+        elems = [meta_element(m[0]) for m in img_metas]
+        if elems[0] != 0 or len(set(elems)) != len(elems):
+            raise ValueError(f'the views of a tile start with the tile itself and are distinct symmetries; got elements {elems}')
+        for m in img_metas:
+            sf = np.asarray(m[0]['scale_factor'], dtype=np.float32).reshape(-1)
+            if (sf != 1).any() or tuple(m[0]['ori_shape'][:2]) != tuple(img_metas[0][0]['ori_shape'][:2]):
+                raise NotImplementedError('multi-scale test views (scale_factor != 1): the device path takes fixed-size tiles')
+        x = self.extract_feat(torch.cat(list(imgs), 0))
+        proposals = self.rpn_head.aug_test_rpn(x, img_metas, elems)
+        return self.roi_head.aug_test(x, proposals, img_metas, elems, rescale=rescale)
 
     @staticmethod
     def _parse_losses(losses):

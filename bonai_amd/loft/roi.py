@@ -384,6 +384,12 @@ class OffsetHeadExpandFeature(_OffsetBase):
         return K.foa_fuse_decode(self._as_four(offset_pred), det_bboxes, self.offset_coder.stds,
                                  img_shape).cpu().numpy().astype(np.float32)
 
+    def merge_view_offsets(self, offset_pred, view_rois, V, table, img_shape=(1024, 1024)):
+        """Test-time augmentation: the head's output for the view-major RoIs [V n,5] -> np.float32 [n,2] in the original frame --
+        get_offsets per view, the vector mapped back, mean over the views, one launch."""
+        return K.tta_merge_offsets(self._as_four(offset_pred), view_rois, V, table, stds=self.offset_coder.stds, max_shape=img_shape,
+                                   foa=True).cpu().numpy().astype(np.float32)
+
 
 @HEADS.register_module()
 class OffsetHead(_OffsetBase):
@@ -427,6 +433,11 @@ class OffsetHead(_OffsetBase):
         o = K.offset_decode(offset_pred, det_bboxes, self.offset_coder.means, self.offset_coder.stds, img_shape,
                             polar=self.offset_coordinate == 'polar')
         return o.cpu().numpy().astype(np.float32)
+
+    def merge_view_offsets(self, offset_pred, view_rois, V, table, img_shape=(1024, 1024)):
+        """Test-time augmentation: see OffsetHeadExpandFeature.merge_view_offsets; offset_decode per view."""
+        return K.tta_merge_offsets(offset_pred, view_rois, V, table, self.offset_coder.means, self.offset_coder.stds, img_shape,
+                                   foa=False, polar=self.offset_coordinate == 'polar').cpu().numpy().astype(np.float32)
 
 
 def _masks_to_device(gt_masks, device):
@@ -719,6 +730,63 @@ class LoftRoIHead(nn.Module):
             # kernels.mask_translate, IoU pairing) -- next to, not instead of, the result tuple
             self.last_device_masks = pasted if self.with_mask else None
             self.last_dets, self.last_det_labels = db, dl              # detection order = the order of the bitmaps and offsets
+        return bbox_results, segm_results, offset_results
+
+    @torch.no_grad()
+    def aug_test(self, x, proposals, img_metas, elems, rescale=False):
+        """Test-time augmentation over the V views of one tile (x: their features as a batch of V; proposals [n,5] in the original
+        frame, from RPNHead.aug_test_rpn; elems: the views' D4 elements) -> simple_test's 3-tuple.  Boxes, scores and masks follow
+        aug_test_bboxes + multiclass_nms and aug_test_mask (test_mixins.py:74-107,179-208, merge_augs.py); the merged offsets are an
+        extension (StandardRoIHead.aug_test, standard_roi_head.py:264-290, returns none).  Every head runs ONCE over all views -- the
+        RoIs of view v carry batch index v -- and the per-view softmax / decode / map back / mean are one launch per result
+        (bonai_amd/csrc/tta.hip).  Views have scale factor 1, so ``rescale`` changes nothing."""
+        dev = x[0].device
+        cfg = self.test_cfg
+        V = len(elems)
+        meta = img_metas[0][0]
+        img_h, img_w = meta['img_shape'][:2]
+        K._tta_check_shape(elems, img_h, img_w)
+        table = K.tta_view_table(elems, dev)
+        ncls = self.bbox_head.num_classes
+        rois = K.tta_view_rois(proposals, table, V, img_h, img_w)
+        cls_score, bbox_pred = self.bbox_head(self.bbox_roi_extractor(x[:self.bbox_roi_extractor.num_inputs], rois))
+        coder = self.bbox_head.bbox_coder
+        bboxes, scores = K.tta_merge_bboxes(rois, bbox_pred, cls_score, V, table, img_h, img_w, coder.means, coder.stds)
+        det_bboxes, det_labels = self.multiclass_nms(bboxes, scores, cfg.score_thr, cfg.nms, cfg.max_per_img)
+        if cfg.get('paste_min_score') is not None and det_bboxes.shape[0]:
+            strong = det_bboxes[:, 4] >= float(cfg['paste_min_score'])
+            det_bboxes, det_labels = det_bboxes[strong], det_labels[strong]
+        db = det_bboxes.cpu().numpy()
+        dl = det_labels.cpu().numpy()
+        bbox_results = [db[dl == i, :] for i in range(ncls)] if db.shape[0] else \
+            [np.zeros((0, 5), dtype=np.float32) for _ in range(ncls)]
+        if det_bboxes.shape[0] == 0:
+            segm = [[] for _ in range(ncls)] if self.with_mask else None
+            return bbox_results, segm, [[] for _ in range(2)]
+        nd = det_bboxes.shape[0]
+        _bboxes = det_bboxes[:, :4].contiguous()
+        det_rois = K.tta_view_rois(_bboxes, table, V, img_h, img_w)
+        segm_results, pasted = None, None
+        if self.with_mask:
+            mask_pred = self.mask_head(self.mask_roi_extractor(x[:self.mask_roi_extractor.num_inputs], det_rois))
+            cls_idx = 0 if self.mask_head.class_agnostic else det_labels.repeat(V)
+            sel = mask_pred[torch.arange(mask_pred.shape[0], device=dev), cls_idx]
+            ori_h, ori_w = meta['ori_shape'][:2]
+            pasted = K.mask_paste_views(sel.reshape(V, nd, sel.shape[-2], sel.shape[-1]), _bboxes, table, ori_h, ori_w,
+                                        cfg.mask_thr_binary)
+            segm_results = [[] for _ in range(ncls)]
+            if cfg.get('rle_masks', False):
+                from ..rle import rle_encode_masks
+                for i, r in enumerate(rle_encode_masks(pasted)):
+                    segm_results[int(dl[i])].append(r)
+            else:
+                im = pasted.bool().cpu().numpy()
+                for i in range(im.shape[0]):
+                    segm_results[int(dl[i])].append(im[i])
+        offset_results = self.offset_head.merge_view_offsets(self._offset_forward(x, det_rois), det_rois, V, table)
+        if cfg.get('keep_device_masks', False):
+            self.last_device_masks = pasted
+            self.last_dets, self.last_det_labels = db, dl
         return bbox_results, segm_results, offset_results
 
     def forward_dummy(self, x, proposals):

@@ -395,3 +395,24 @@ class RPNHead(nn.Module):
     def simple_test_rpn(self, x, img_metas):
         fused = self.forward_fused(x)
         return self.get_bboxes_fused(fused, img_metas)
+
+    @torch.no_grad()
+    def aug_test_rpn(self, x, img_metas, elems):
+        """rpn_test_mixin.py:40-60 + merge_aug_proposals (merge_augs.py:8-47) for the V views of one tile, x the features of the views
+        as a batch of V: one get_bboxes_fused for the batch, every view's proposals mapped back and concatenated in one launch,
+        NMS at test_cfg.nms_thr, the best max_num by score.  -> proposals [n,5] in the original frame."""
+        cfg = self.test_cfg
+        metas = [m[0] for m in img_metas]
+        V = len(metas)
+        props, counts = self.get_bboxes_fused(self.forward_fused(x), metas)
+        if V * props.shape[1] > K.NMS_MAX_SEGMENT:
+            raise NotImplementedError(f'{V} views x {props.shape[1]} proposals = {V * props.shape[1]} boxes in one NMS segment; the '
+                                      f'segmented NMS takes at most {K.NMS_MAX_SEGMENT} (kernels.NMS_MAX_SEGMENT): lower '
+                                      'test_cfg.rpn.max_num / nms_post or use fewer views')
+        h, w = metas[0]['img_shape'][:2]
+        K._tta_check_shape(elems, h, w)
+        merged = K.tta_gather_proposals(props, counts, K.tta_view_table(elems, props.device), h, w)
+        if merged.shape[0] == 0:
+            return merged
+        dets, _ = K.nms(merged[:, :4].contiguous(), merged[:, 4].contiguous(), cfg.nms_thr, predicate=cfg.get('nms_predicate', 'device'))
+        return dets[:min(int(cfg.max_num), dets.shape[0])]        # (K.nms returns score-descending order)

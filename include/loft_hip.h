@@ -648,6 +648,35 @@ int loft_image_prep_d4(const uint8_t* img, const int32_t* elems, int n, int H, i
                        float mean2, float std0, float std1, float std2, float* out, void* stream);
 int loft_mask_d4_u8(const uint8_t* masks, int K, int H, int W, int elem, uint8_t* out, void* stream);
 
+/* ---- test-time augmentation over the square's symmetries (bonai_amd/csrc/tta.hip) ---------------------------------------------------
+ * The merges of mmdet/core/post_processing/merge_augs.py and the aug_test_* mixins for V views of ONE tile, V <= 8.  views: DEVICE
+ * int32 [V], one LOFT_D4_* element per view; img_h x img_w: the original tile (a transposing view's image is img_w x img_h).  A box
+ * goes into a view by transpose, x-mirror, y-mirror in that order -- a mirror is the reference's bbox_flip, x1' = W - x2,
+ * x2' = W - x1 in fp32 -- and back by the same steps in reverse order; the scale factor is 1.  A mean over views is the sequential
+ * fp32 sum in view order divided by V.  n == 0 launches nothing.
+ * loft_tta_view_rois:        boxes [n,4] (original frame) -> rois [V*n,5] view-major, row (v, i) = (v, box i in view v).
+ * loft_tta_gather_proposals: props [V,P,5] + counts int64 [V] (device) -> out [out_rows,5], the first counts[v] rows of every view
+ *                            mapped back, views concatenated in order, scores kept; out_rows = sum(counts) (rows past it are dropped).
+ * loft_tta_merge_bboxes:     rois [V*n,5], bbox_pred [V*n,4*Cb] (Cb = C, or 1: class-agnostic), cls_score [V*n,C+1]; per view softmax
+ *                            and delta2bbox clipped to the VIEW's image shape, mapped back; -> bboxes [n,4*Cb], scores [n,C+1].
+ * loft_tta_merge_offsets:    rois [V*n,5] = the view boxes; pred = one run of the offset head over them: reg_num 0: FOA pred
+ *                            [4,V*n,2] branch-major (loft_foa_fuse_decode per view), reg_num 2 | 3: pred [V*n,reg_num]
+ *                            (loft_offset_decode per view); the decoded vector goes back through the
+ *                            inverse element (a mirror negates a component, a transpose swaps them) -> out [n,2].
+ * loft_mask_paste_views:     logits [V,N,S,S] (class selected, S <= 64), boxes [N,4] original frame -> out uint8 {0,1}
+ *                            [N,img_h,img_w]: loft_mask_paste of the mean over views of sigmoid(logit) read through each view's
+ *                            inverse permutation of the S x S grid; the merged probabilities live in LDS only. */
+int loft_tta_view_rois(const float* boxes, int64_t n, const int32_t* views, int V, int img_h, int img_w, float* rois, void* stream);
+int loft_tta_gather_proposals(const float* props, const int64_t* counts, int V, int P, const int32_t* views, int img_h, int img_w,
+                              int64_t out_rows, float* out, void* stream);
+int loft_tta_merge_bboxes(const float* rois, const float* bbox_pred, const float* cls_score, int64_t n, int V, int C, int Cb,
+                          const int32_t* views, int img_h, int img_w, const float* means_host, const float* stds_host,
+                          float wh_ratio_clip, float* bboxes, float* scores, void* stream);
+int loft_tta_merge_offsets(const float* pred, const float* rois, int64_t n, int V, int reg_num, const int32_t* views, float mean_x,
+                           float mean_y, float std_x, float std_y, float max_h, float max_w, int polar, float* out, void* stream);
+int loft_mask_paste_views(const float* logits, const float* boxes, int N, int V, int S, const int32_t* views, int img_h, int img_w,
+                          float thr, uint8_t* out, void* stream);
+
 /* ---- sparse backward of the RPN head -------------------------------------------------------------
  * The RPN losses (anchor_head.py:429-497, rpn_head.py:56-80) read the head outputs only at the sampled anchors (<= 256 per
  * image of 261 888), so its backward runs on the selected pixels: level_ptrs/H/W (HOST arrays, n_levels <= 8) describe the

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Entry point with the argv surface of the reference's tools/test.py:17-67 for the LOFT hot path.
 
-    python tools/test.py CONFIG [CHECKPOINT] [--out results.pkl] [--eval] [--ann-file F --img-prefix D] [--num N]
+    python tools/test.py CONFIG [CHECKPOINT] [--out results.pkl] [--eval] [--ann-file F --img-prefix D] [--num N] [--tta h,v,r90]
 
 Dataset mode (the annotation file of ``cfg.data.test`` -- or ``--ann-file`` -- exists): every image of the file goes through
 `model(return_loss=False, rescale=True, img=[...], img_metas=[[...]])` with samples_per_gpu = 1 (apis/test.py:26,53-72), results
@@ -34,6 +34,9 @@ def main():
     ap.add_argument('--img-prefix', help='tile directory (default: cfg.data.test.img_prefix)')
     ap.add_argument('--score-thr', type=float, default=0.4, help='evaluation: detections below are dropped (bonai_evaluation.py:30)')
     ap.add_argument('--min-area', type=float, default=500, help='evaluation: roofs smaller than this many pixels are dropped (:31)')
+    ap.add_argument('--tta', help="test-time augmentation views, a comma-separated subset of h,v,r90,r180,r270 (overrides the "
+                                  "MultiScaleFlipAug entry of cfg.data.test.pipeline); flips mirror the reference, rotations and "
+                                  "the merged offsets are extensions")
     ap.add_argument('--synthetic', action='store_true')
     ap.add_argument('--num', type=int, default=4, help='synthetic mode: number of tiles')
     ap.add_argument('--size', type=int, default=1024)
@@ -56,6 +59,11 @@ def main():
     dataset_mode = not args.synthetic and files and all(os.path.exists(f) for f in files)
     if not dataset_mode and not args.bitmap_masks:
         cfg.test_cfg.rcnn['rle_masks'] = True
+    from bonai_amd import tta
+    tile = tuple(tcfg.get('img_scale', (1024, 1024)))[::-1] if dataset_mode else (args.size, args.size)
+    views = tta.parse_tta_arg(args.tta, tile) if args.tta else tta.views_from_pipeline(tcfg.get('pipeline'), tile)
+    if views is not None and len(views) == 1:
+        views = None
     model = build_detector(cfg.model, train_cfg=None, test_cfg=cfg.test_cfg)
     if args.checkpoint:
         from bonai_amd.checkpoint import load_checkpoint
@@ -66,7 +74,7 @@ def main():
         from bonai_amd import evaluation as E
         from bonai_amd.dataset import BonaiDataset
         extra = {k: tcfg[k] for k in ('bbox_type', 'mask_type', 'offset_coordinate', 'resolution', 'classes') if k in tcfg}
-        ds = BonaiDataset(ann, prefix, test_mode=True, **extra)
+        ds = BonaiDataset(ann, prefix, test_mode=True, test_views=views, **extra)
         results, records = run_dataset(model, ds, evaluate=args.eval, eval_kw=dict(score_thr=args.score_thr, min_area=args.min_area))
         torch.cuda.synchronize()
         print(f'{len(ds) / (time.time() - t0):.2f} img/s (decode + inference + mask paste + RLE' + (' + evaluation)' if args.eval else ')'))
@@ -78,8 +86,13 @@ def main():
         results = []
         for i in range(args.num):
             data = make_batch(1, args.size, 40, step=i, device='cuda')
+            imgs, metas = [data['img']], [data['img_metas']]
+            if views is not None:                       # the views of the synthetic tile (a dataset builds them in one launch)
+                from bonai_amd.data import d4_apply
+                imgs = [torch.from_numpy(d4_apply(data['img'].cpu().numpy(), tta.view_element(v), axes=(2, 3)).copy()).cuda() for v in views]
+                metas = [[tta.view_meta(data['img_metas'][0], v)] for v in views]
             with torch.no_grad():
-                res = model(img=[data['img']], img_metas=[data['img_metas']], return_loss=False, rescale=True)
+                res = model(img=imgs, img_metas=metas, return_loss=False, rescale=True)
             results.append(res)
             print(f'[{i + 1}/{args.num}] dets={res[0][0].shape[0]} offsets={res[2].shape if hasattr(res[2], "shape") else 0}', flush=True)
         torch.cuda.synchronize()
