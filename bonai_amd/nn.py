@@ -38,33 +38,53 @@ def _direct_slot(p):
     return g if (g.dtype == torch.float32 and g.is_contiguous() and g.shape == p.shape) else None
 
 
-def _mark_sunk(*ps):
-    """These parameters' gradients of this step reach the arena through the kernels (now or at the next queue flush), not
-    through autograd: the trainer's reducer must not treat autograd's own post-accumulate callback as 'gradient ready'."""
-    for p in ps:
-        if p is not None:
-            p._loft_sunk = True
+# ---- depositing a parameter gradient in the arena: ONE plan (_deposit_slots) and ONE commit (_deposit) for every backward node --
+# A node either deposits its packed weight gradient dwp (+ bias / BN gradient db) in its parameters' arena slots -- autograd then
+# gets None for those inputs -- or unpacks and returns it.  The plan needs no gradient: it is made BEFORE the weight-gradient
+# launch, because only a record bound for the unpack queue may come as split-K slots (conv2d_wgrad(slots_ok=...)).
+
+def _deposit_slots(pw, pb=None, pbn=None):
+    """The arena slots (dW, dgamma | None, dbeta-or-dbias | None) of one record, or None unless the weight ``pw`` and everything
+    that must go with it has one: its BN pair ``pbn`` = (gamma, beta) Parameters, else its bias Parameter ``pb``."""
+    pg, pb = pbn if pbn is not None else (None, pb)
+    slots = _direct_slot(pw), None if pg is None else _direct_slot(pg), None if pb is None else _direct_slot(pb)
+    ok = slots[0] is not None and (pg is None or slots[1] is not None) and (pb is None or slots[2] is not None)
+    return slots if ok else None
+
+
+def _nsplit(dwp):
+    """Split-K slots of a weight gradient that came back as [G, S, T, Cout, Cin] (kernels.conv_wgrad(slots_ok=True)), else 1."""
+    return dwp.shape[1] if dwp.dim() == 5 else 1
+
+
+def _deposit(dwp, db, w, bn, eps, slots, sinks, flat_chw=None, nsplit=1):
+    """Deposit one record in ``slots`` (a _deposit_slots plan): through the unpack queue when the trainer has one open, else with
+    a launch of its own.  ``sinks``: the Parameters whose use the record completes -- marked as sunk (the trainer's reducer must
+    not take autograd's own post-accumulate callback for 'gradient ready') and reported to the sink once the deposit is enqueued.
+    flat_chw = (C, H, W): w is [O, C H W] and dwp [O, (H W) C] (tap-major K order); nsplit > 1: dwp is [nsplit][...] split-K slots."""
+    for p in sinks:
+        p._loft_sunk = True
+    if UNPACK_Q is not None:
+        UNPACK_Q.add(dwp, db, w, bn, eps, slots, [(lambda q=q: _sink_done(q)) for q in sinks], flat_chw=flat_chw, nsplit=nsplit,
+                     params=sinks)
+    else:
+        K.fold_unpack_bwd(dwp, db, w, bn, eps, out=slots)
+        for p in sinks:
+            _sink_done(p)
 
 
 def _queue_param_grads(jobs):
-    """jobs: [(weight Parameter, dW fp32 [Cout, Cin(P)] (a view is fine), bias Parameter | None, db fp32 [Cout] | None, flat_chw)].
+    """The leaf heads' entry (narrow heads, the sparse RPN backward), all or nothing over
+    jobs: [(weight Parameter, dW fp32 [Cout, Cin(P)] (a view is fine), bias Parameter | None, db fp32 [Cout] | None, flat_chw)].
     When the trainer's unpack queue is open and every parameter has an arena slot, the gradients are deposited there by the next
-    batched unpack launch (no per-parameter accumulation launch of autograd) and True is returned: the caller hands autograd None.
-    flat_chw = (C, H, W): the weight is [O, C, H, W] and dW is [O, (H W) C] (tap-major K order)."""
+    batched unpack launch (no per-parameter accumulation launch of autograd) and True is returned: the caller hands autograd None."""
     if UNPACK_Q is None or DBG.no_leaf_sink:
         return False
-    slots = []
-    for pw, dw, pb, db, flat in jobs:
-        sw = _direct_slot(pw)
-        sb = _direct_slot(pb) if pb is not None else None
-        if sw is None or (pb is not None and (sb is None or db is None)):
-            return False
-        slots.append((sw, sb))
-    for (pw, dw, pb, db, flat), (sw, sb) in zip(jobs, slots):
-        sinks = [pw] + ([pb] if pb is not None else [])
-        _mark_sunk(*sinks)
-        UNPACK_Q.add(dw, db if pb is not None else None, pw, None, 1e-5, (sw, None, sb), [(lambda q=q: _sink_done(q)) for q in sinks],
-                     flat_chw=flat, params=sinks)
+    plans = [None if (pb is not None and db is None) else _deposit_slots(pw, pb) for pw, dw, pb, db, flat in jobs]
+    if any(slots is None for slots in plans):
+        return False
+    for (pw, dw, pb, db, flat), slots in zip(jobs, plans):
+        _deposit(dw, db if pb is not None else None, pw, None, 1e-5, slots, [pw] if pb is None else [pw, pb], flat_chw=flat)
     return True
 
 
@@ -73,6 +93,13 @@ def _count_uses(*ps):
     for p in ps:
         if isinstance(p, torch.nn.Parameter) and p.requires_grad:
             p._loft_pending = getattr(p, '_loft_pending', 0) + 1
+
+
+def _uncount_uses(ps):
+    """Take back uses counted in forward: the backward returns these gradients to autograd after all (nothing is sunk)."""
+    for p in ps:
+        if p is not None and getattr(p, '_loft_pending', 0) > 0:
+            p._loft_pending -= 1
 
 
 def _sink_done(p):
@@ -309,59 +336,46 @@ class _ConvFn(torch.autograd.Function):
         need_b = (has_b and any(ctx.needs_input_grad[3 + 2 * i + 1] for i in range(G))) or \
             (bn_stats is not None and (ctx.needs_input_grad[3 + 2 * G] or ctx.needs_input_grad[3 + 2 * G + 1]))
         if need_w or need_b:
-            # every group's gradient goes to the batched unpack (which can sum split-K slots while it reads) when all of its
-            # parameters have arena slots; else the atomically combined form every other consumer expects
-            queued = UNPACK_Q is not None and need_w and all(
-                _direct_slot(ctx.params[2 * i]) is not None for i in range(G)) and (
-                bn_stats is None or (_direct_slot(ctx.params[2 * G]) is not None and _direct_slot(ctx.params[2 * G + 1]) is not None))
+            bn = pbn = None
+            eps = 1e-5
+            if bn_stats is not None:
+                bn = (tensors[2 * G], tensors[2 * G + 1], bn_stats[0], bn_stats[1])
+                pbn, eps = ctx.params[2 * G:2 * G + 2], bn_stats[2]
+            # one record per group, deposited when its weight and the folded BN pair have arena slots.  When every group's goes to
+            # the batched unpack, the gradient may come as split-K slots (the unpack sums them while it reads); else it comes in
+            # the atomically combined form every other consumer expects
+            plans = [_deposit_slots(ctx.params[2 * i], None, pbn) if need_w else None for i in range(G)]
+            queued = UNPACK_Q is not None and all(slots is not None for slots in plans)
             if need_b:
                 dwp, db = K.conv2d_wgrad(g, x, R, S, stride, pad, groups=G, with_bias=True, slots_ok=queued)
             else:
                 dwp, db = K.conv2d_wgrad(g, x, R, S, stride, pad, groups=G, slots_ok=queued), None
-            nsp = _nsplit(dwp)
-            bn = None
-            if bn_stats is not None:
-                bn = (tensors[2 * G], tensors[2 * G + 1], bn_stats[0], bn_stats[1])
+            nsp, returned = _nsplit(dwp), False
             for i in range(G):
-                pw = ctx.params[2 * i]
-                slot_w = _direct_slot(pw) if need_w else None
-                slot_g = slot_b = None
-                if bn is not None and slot_w is not None:
-                    slot_g, slot_b = _direct_slot(ctx.params[2 * G]), _direct_slot(ctx.params[2 * G + 1])
-                if slot_w is not None and (bn is None or (slot_g is not None and slot_b is not None)):
-                    # accumulate straight into the flat gradient arena; autograd gets None for these inputs
-                    eps = bn_stats[2] if bn_stats is not None else 1e-5
-                    if UNPACK_Q is not None:
-                        sinks = [pw]
-                        pb = ctx.params[2 * i + 1] if (bn is None and has_b and db is not None) else None
-                        if pb is not None and ctx.needs_input_grad[3 + 2 * i + 1]:
-                            slot_b = _direct_slot(pb)           # the conv's own bias gradient: db rides in the same launch
-                            if slot_b is not None:
-                                sinks.append(pb)
-                        if bn is not None and i == G - 1:
-                            sinks += [ctx.params[2 * G], ctx.params[2 * G + 1]]
-                        _mark_sunk(*sinks)
-                        UNPACK_Q.add(dwp[i], None if db is None else db[i], ws[i], bn, eps, (slot_w, slot_g, slot_b),
-                                     [(lambda q=q: _sink_done(q)) for q in sinks], nsplit=nsp, params=sinks)
-                        if has_b and db is not None and bn is None and slot_b is None:
-                            ngrads[2 * i + 1] = db[i][:ws[i].shape[0]]
-                        continue
-                    _mark_sunk(pw, *((ctx.params[2 * G], ctx.params[2 * G + 1]) if bn is not None else ()))
-                    K.fold_unpack_bwd(dwp[i], None if db is None else db[i], ws[i], bn, eps, out=(slot_w, slot_g, slot_b))
-                    _sink_done(pw)
+                slots, dbi = plans[i], None if db is None else db[i]
+                if slots is None:
+                    returned = True
+                    ngrads[2 * i], dg, dbeta = K.fold_unpack_bwd(dwp[i], dbi, ws[i], bn, eps, need_dw=need_w)
+                    if bn is not None:
+                        ngrads[2 * G], ngrads[2 * G + 1] = dg, dbeta
+                else:
+                    sinks = [ctx.params[2 * i]]
+                    if UNPACK_Q is not None and bn is None and has_b and db is not None and ctx.needs_input_grad[3 + 2 * i + 1]:
+                        # the conv's own bias gradient rides in the same queue record when the bias has a slot (else it alone
+                        # goes back to autograd); the launch without a queue deposits weights and BN gradients only
+                        pb = ctx.params[2 * i + 1]
+                        slot_b = _direct_slot(pb)
+                        if slot_b is not None:
+                            slots = (slots[0], None, slot_b)
+                            sinks.append(pb)
                     if bn is not None and i == G - 1:
-                        _sink_done(ctx.params[2 * G])
-                        _sink_done(ctx.params[2 * G + 1])
-                    if has_b and db is not None:
-                        ngrads[2 * i + 1] = db[i][:ws[i].shape[0]]
-                    continue
-                dw, dg, dbeta = K.fold_unpack_bwd(dwp[i], None if db is None else db[i], ws[i], bn,
-                                                  bn_stats[2] if bn_stats is not None else 1e-5, need_dw=need_w)
-                ngrads[2 * i] = dw
-                if has_b and db is not None:
+                        sinks += pbn                 # (the BN pair is shared by the groups: its use ends with the last record)
+                    _deposit(dwp[i], dbi, ws[i], bn, eps, slots, sinks, nsplit=nsp)
+                if has_b and db is not None and (slots is None or slots[2] is None):
                     ngrads[2 * i + 1] = db[i][:ws[i].shape[0]]
-                if bn is not None:
-                    ngrads[2 * G], ngrads[2 * G + 1] = dg, dbeta
+                    returned = True
+            if returned:                 # (autograd accumulates these: the uses counted in forward are not sunk)
+                _uncount_uses(p for p, gr in zip(ctx.params, ngrads) if gr is not None)
         gres = g if (ctx.has_res and ctx.needs_input_grad[1]) else None
         return (None if join_deposit else gx, gres, None) + tuple(ngrads)
 
@@ -477,15 +491,12 @@ class _LinearFn(torch.autograd.Function):
         gw = gb = None
         need_w, need_b = ctx.needs_input_grad[1], pb is not None and ctx.needs_input_grad[2]
         if need_w or need_b:
-            slot_w = _direct_slot(pw) if need_w else None
-            slot_b = _direct_slot(pb) if need_b else None
-            queued = UNPACK_Q is not None and slot_w is not None and (not need_b or slot_b is not None)
-            dwp, db = K.conv2d_wgrad(g4, x4, 1, 1, 1, 0, with_bias=True, slots_ok=queued)
-            if queued:
-                sinks = [pw] + ([pb] if need_b else [])
-                _mark_sunk(*sinks)
-                UNPACK_Q.add(dwp[0, :, 0] if dwp.dim() == 5 else dwp[0, 0], db[0], w, None, 1e-5, (slot_w, None, slot_b),
-                             [(lambda q=q: _sink_done(q)) for q in sinks], flat_chw=flat_chw, nsplit=_nsplit(dwp), params=sinks)
+            # (deposited through the queue only: undoing the flat_chw column order is the batched unpack's)
+            slots = _deposit_slots(pw, pb if need_b else None) if (UNPACK_Q is not None and need_w) else None
+            dwp, db = K.conv2d_wgrad(g4, x4, 1, 1, 1, 0, with_bias=True, slots_ok=slots is not None)
+            if slots is not None:
+                _deposit(dwp[0, :, 0] if dwp.dim() == 5 else dwp[0, 0], db[0], w, None, 1e-5, slots, [pw, pb] if need_b else [pw],
+                         flat_chw=flat_chw, nsplit=_nsplit(dwp))
             else:
                 gw = dwp[0, 0, :O, :Kd]
                 if flat_chw is not None:
@@ -561,11 +572,8 @@ class _NarrowHeadFn(torch.autograd.Function):
             if ctx.leaves is not None and dw is not None and (db is not None or not ctx.has_b) and _queue_param_grads(
                     [(pw, dw[lo:hi], pb, None if (pb is None or db is None) else db[lo:hi], None) for pw, pb, lo, hi in ctx.leaves]):
                 return gx, None, None, None, None, None, None, None, None
-            if ctx.leaves is not None:      # (no queue / no slots: autograd accumulates; the uses counted in forward are not sunk)
-                for l in ctx.leaves:
-                    for p_ in l[:2]:
-                        if p_ is not None and getattr(p_, '_loft_pending', 0) > 0:
-                            p_._loft_pending -= 1
+            if ctx.leaves is not None:      # (no queue / no slots: autograd accumulates)
+                _uncount_uses(p for l in ctx.leaves for p in l[:2])
             return gx, (dw.view(w.shape) if dw is not None else None), db, None, None, None, None, None, None
         P = _NarrowHeadFn.PADW
         N, c4, H, W = g.shape
@@ -590,10 +598,7 @@ class _NarrowHeadFn(torch.autograd.Function):
         if want_b:
             gb = g[:, :Cout].float().sum(dim=(0, 2, 3))
         if ctx.leaves is not None:
-            for l in ctx.leaves:
-                for p_ in l[:2]:
-                    if p_ is not None and getattr(p_, '_loft_pending', 0) > 0:
-                        p_._loft_pending -= 1
+            _uncount_uses(p for l in ctx.leaves for p in l[:2])
         return gx, gw, gb, None, None, None, None, None, None
 
 
@@ -665,7 +670,9 @@ def modulated_deform_conv2d(x, w, b, w_off, b_off, stride=1, pad=0, dil=1, defor
 
 
 class _DeconvFn(torch.autograd.Function):
-    """ConvTranspose2d(k=2, s=2) + bias + ReLU (mmdet/models/roi_heads/mask_heads/fcn_mask_head.py:121-124)."""
+    """ConvTranspose2d(k=2, s=2) + bias + ReLU (mmdet/models/roi_heads/mask_heads/fcn_mask_head.py:121-124).
+    Its weight gradient is returned to autograd, not deposited (_deposit): the weight is [Cin, Cout, 2, 2], a layout the unpack
+    kernels do not write, so the backward permutes a view of the packed gradient and autograd accumulates it (one node per step)."""
 
     @staticmethod
     def forward(ctx, x, w, b, input_relu=False, head=None):
@@ -1198,9 +1205,7 @@ class _SparseRPNFn(torch.autograd.Function):
             pgrads = (None,) * 6
         else:
             # (no queue / no slots: autograd accumulates; the uses counted in forward are not sunk -- as _NarrowHeadFn does)
-            for p_, need in zip(ctx.params, ctx.needs_input_grad[5:11]):
-                if need and p_ is not None and getattr(p_, '_loft_pending', 0) > 0:
-                    p_._loft_pending -= 1
+            _uncount_uses(p for p, need in zip(ctx.params, ctx.needs_input_grad[5:11]) if need)
             pgrads = (g_wconv, dbc[0], g_wcls, g_bcls, g_wreg, g_breg)
         return (None, None, None, None, None) + pgrads + tuple(ret) + (None,) * len(xs)
 
@@ -1236,11 +1241,6 @@ def _rb_pack(w, bn, cin_p, cout_p, need_dgrad, pdt):
     return out
 
 
-def _nsplit(dwp):
-    """Split-K slots of a weight gradient that came back as [G, S, T, Cout, Cin] (kernels.conv_wgrad(slots_ok=True)), else 1."""
-    return dwp.shape[1] if dwp.dim() == 5 else 1
-
-
 def _rb_param_grads(g, x, w, bn, k, stride, pad, needs):
     """Weight / gamma / beta gradients of one conv+bn from the (already ReLU-masked) output gradient g and the conv input x.
     Returns (dw, dgamma, dbeta) for autograd, or Nones when the kernels accumulated straight into the trainer's arena."""
@@ -1248,9 +1248,10 @@ def _rb_param_grads(g, x, w, bn, k, stride, pad, needs):
     if not (need_w or need_g or need_b):
         return None, None, None
     bnt = (bn.weight, bn.bias, bn.running_mean, bn.running_var)
-    slots = (_direct_slot(w) if need_w else None, _direct_slot(bn.weight) if need_g else None, _direct_slot(bn.bias) if need_b else None)
-    sunk = need_w and need_g and need_b and all(s is not None for s in slots)
-    if sunk and UNPACK_Q is not None and WGRAD_STREAM is not None and g.is_cuda and K.PROFILE is None:
+    sinks = (w, bn.weight, bn.bias)
+    slots = _deposit_slots(w, None, sinks[1:]) if (need_w and need_g and need_b) else None       # (all three, or autograd)
+    queued = slots is not None and UNPACK_Q is not None
+    if queued and WGRAD_STREAM is not None and g.is_cuda and K.PROFILE is None:
         # Nothing on the data-gradient chain reads a weight gradient, so the launch goes to a second stream and runs beside
         # the next blocks' dgrad kernels (its split-K atomics tail and its < 256-workgroup grids leave CUs idle otherwise);
         # the unpack queue waits for it with an event (UnpackQueue.add / flush).
@@ -1258,21 +1259,13 @@ def _rb_param_grads(g, x, w, bn, k, stride, pad, needs):
         WGRAD_STREAM.wait_stream(cur)
         g.record_stream(WGRAD_STREAM)
         x.record_stream(WGRAD_STREAM)
-        _mark_sunk(w, bn.weight, bn.bias)
         with torch.cuda.stream(WGRAD_STREAM):
             dwp, db = K.conv2d_wgrad(g, x, k, k, stride, pad, with_bias=True, slots_ok=True)
-            UNPACK_Q.add(dwp[0], db[0], w, bnt, bn.eps, slots, [(lambda q=q: _sink_done(q)) for q in (w, bn.weight, bn.bias)],
-                         nsplit=_nsplit(dwp), params=(w, bn.weight, bn.bias))
+            _deposit(dwp[0], db[0], w, bnt, bn.eps, slots, sinks, nsplit=_nsplit(dwp))
         return None, None, None
-    dwp, db = K.conv2d_wgrad(g, x, k, k, stride, pad, with_bias=True, slots_ok=sunk and UNPACK_Q is not None)
-    if sunk:
-        _mark_sunk(w, bn.weight, bn.bias)
-        if UNPACK_Q is not None:
-            UNPACK_Q.add(dwp[0], db[0], w, bnt, bn.eps, slots, [(lambda q=q: _sink_done(q)) for q in (w, bn.weight, bn.bias)],
-                         nsplit=_nsplit(dwp), params=(w, bn.weight, bn.bias))
-            return None, None, None
-        K.fold_unpack_bwd(dwp[0], db[0], w, bnt, bn.eps, out=slots)
-        _sink_done(w), _sink_done(bn.weight), _sink_done(bn.bias)
+    dwp, db = K.conv2d_wgrad(g, x, k, k, stride, pad, with_bias=True, slots_ok=queued)
+    if slots is not None:
+        _deposit(dwp[0], db[0], w, bnt, bn.eps, slots, sinks, nsplit=_nsplit(dwp))
         return None, None, None
     dw, dg, dbeta = K.fold_unpack_bwd(dwp[0], db[0], w, bnt, bn.eps, need_dw=need_w)
     return (dw if need_w else None), (dg if need_g else None), (dbeta if need_b else None)

@@ -88,6 +88,49 @@ def test_every_debug_switch_alone_matches_the_default_step(first_k):
     _compare(want, m, 'default after the switches')
 
 
+def test_grouped_conv_deposits_its_weights_and_returns_a_slotless_bias_to_autograd():
+    """The one deposit path the switches above do not isolate: a grouped conv node (two branches, one launch) with conv biases
+    under an open unpack queue and a sink, where one bias has no arena slot (its .grad is not contiguous).  Both weights and the
+    other bias land in their slots through the queue, the slotless bias alone comes back through autograd, every value equals
+    the all-autograd run (1e-2 relative in norm: the sink-vs-autograd bound of tests/test_edge_gpu.py) and no use count is left."""
+    from bonai_amd import kernels as K
+    from bonai_amd import nn as F2
+    torch.manual_seed(0)
+    G, C, B = 2, 64, 2
+    ws = [torch.nn.Parameter(torch.randn(C, C, 3, 3, device='cuda') * 0.05) for _ in range(G)]
+    bs = [torch.nn.Parameter(torch.randn(C, device='cuda') * 0.1) for _ in range(G)]
+    params = ws + bs
+    x = torch.randn(G * B, C, 16, 16, device='cuda').to(K.L.act16()).contiguous(memory_format=torch.channels_last)
+    gy = torch.randn(G * B, C, 16, 16, device='cuda').to(K.L.act16()).contiguous(memory_format=torch.channels_last)
+
+    def step():
+        F2.conv2d(x, ws, bs, pad=1, relu=True, groups=G).backward(gy)
+    assert F2.GRAD_SINK is None and F2.UNPACK_Q is None
+    step()                                                # all-autograd
+    torch.cuda.synchronize()
+    want = [p.grad.clone() for p in params]
+    slots = [torch.zeros_like(p) for p in params]
+    slots[3] = torch.zeros(C, 2, device='cuda')[:, 0]     # the right shape and dtype, not contiguous: no slot
+    for p, s in zip(params, slots):
+        p.grad, p._loft_pending, p._loft_sunk = s, 0, False
+    fired = []
+    F2.GRAD_SINK, F2.UNPACK_Q = fired.append, K.UnpackQueue()
+    try:
+        step()
+        assert fired == []                                # (queued: nothing is reported before the launch that serves it)
+        F2.UNPACK_Q.flush()
+    finally:
+        F2.GRAD_SINK = F2.UNPACK_Q = None
+    torch.cuda.synchronize()
+    assert [id(p) for p in fired] == [id(p) for p in (ws[0], bs[0], ws[1])]
+    assert [getattr(p, '_loft_sunk', False) for p in params] == [True, True, True, False]
+    for p, s, w in zip(params, slots, want):
+        assert p.grad is s, 'the gradient did not stay in its slot'
+        print('grouped deposit: |got - want| / |want| =', (s - w).norm().item() / w.norm().item())
+        assert (s - w).norm().item() <= 1e-2 * w.norm().item() + 1e-7
+    assert [p._loft_pending for p in params] == [0, 0, 0, 0]
+
+
 def test_fp32_mode_trainer_shares_operand_planes_across_streams_safely(first_k):
     """in the fp32 parity mode a residual block's backward splits its output gradient into operand planes ONCE, on the
     weight-gradient side stream, and the data gradient on the main stream takes them from the memo; the forward's cached planes are
