@@ -25,9 +25,11 @@
 //     sorted in LDS by the window pixel they land on, then accumulated in registers per pixel; no float atomics at all.
 //   * window   (fp32 parity / test path) -- lane = channel, fp32 LDS window with wave-private rows.
 //   * generic  (any deform_groups / C % 8 == 0) -- global fp32 atomics (~2.3 G transactions/s on MI355X: slow, kept for coverage).
+// loft_mdcn_sample_bwd_v runs the family (and split count / channels per lane) the caller names; loft_mdcn_bwd_form answers,
+// on the host alone, which one a launch takes (mdcn_plan is the one place that decides).
 // Both tiled kernels store per-tile gradient windows to a workspace; mdcn_window_gather_kernel sums the overlaps.
-// Measured (tools/bench_mdcn.py, 8 x 256 x 256^2 bf16 3x3): generic 15.7 ms avg per launch -> binned 4.6 ms at the largest
-// shape (fwd 1.3 ms).
+// Measured (tools/bench_mdcn.py, 8 x 256 x 256^2 bf16 3x3): generic 15.7 ms avg per launch -> binned 4.7 ms at the largest
+// shape (fwd 1.2 ms).
 #include "loft_common.h"
 #include "../../include/loft_hip.h"
 #include <stdlib.h>
@@ -154,7 +156,10 @@ __global__ __launch_bounds__(256) void mdcn_sample_bwd_kernel(const T* __restric
     build_items(a, om, m0, npix, items, raw);
     const int K = a.kh * a.kw, KG = K * a.DG;
     const int cg = a.C >> 3, cpg = cg / a.DG;
-    const int seg = cpg < 64 ? cpg : 64;                // lanes of one item inside a wave (power of two, C % (8*DG) == 0)
+    // Lanes of one item that reduce with shuffles: the item's cpg lanes when cpg is a power of two, capped at a wave; any other
+    // cpg (C = 72, 192) goes lane by lane through the LDS atomics.  The xor-shuffle reduction is valid because the segments are
+    // aligned: an item's lanes start at i = (p*K + k)*cg + g*cpg, a multiple of seg (cg = cpg*DG), and blockDim.x % seg == 0.
+    const int seg = (cpg & (cpg - 1)) ? 1 : (cpg < 64 ? cpg : 64);
     const int total = npix * K * cg;
     const int rounds = (total + blockDim.x - 1) / blockDim.x;
     for (int r = 0; r < rounds; ++r) {
@@ -205,7 +210,7 @@ __global__ __launch_bounds__(256) void mdcn_sample_bwd_kernel(const T* __restric
             sdm += __shfl_xor(sdm, o, 64);
         }
         if (live && ((threadIdx.x & (seg - 1)) == 0)) {
-            if (cpg <= 64) {            // the segment is the whole item: plain store
+            if (seg == cpg) {           // the segment is the whole item: plain store
                 red[item_idx][0] = sdy; red[item_idx][1] = sdx; red[item_idx][2] = sdm;
             } else {                    // several segments per item: LDS atomics
                 atomicAdd(&red[item_idx][0], sdy); atomicAdd(&red[item_idx][1], sdx); atomicAdd(&red[item_idx][2], sdm);
@@ -487,7 +492,11 @@ __global__ __launch_bounds__(256) void mdcn_sample_bwd_bin_kernel(const bf16_t* 
         if (lane == 0) start[npix] = run;
     }
     __syncthreads();
-    for (int i = tid; i < nitems * 4; i += 256) {
+    // One wave fills, in item order: the place of an entry in its pixel's list -- and with it the order of the fp32 additions
+    // of step 3 -- then does not depend on how four waves' cursor atomics interleave, and dx is the same bits on every launch
+    // (36 short rounds instead of 9.  Measured, tools/bench_mdcn.py, 8 x 256 x 256^2: 4.76 ms against 4.72 ms with all four waves
+    // filling, +1.0 %; +1.7 % at 8 x 256 x 64^2.)
+    if (wave == 0) for (int i = lane; i < nitems * 4; i += 64) {
         int pix = 0; float wt = 0.f;
         if (corner(i, pix, wt) == 1) {
             const int pos = atomicAdd(&cnt[pix], 1);
@@ -631,8 +640,6 @@ int mdcn_check(const MdcnArgs& a) {
     const int K = a.kh * a.kw;
     if (K < 1 || K > MDCN_MAXK || a.DG < 1 || a.DG > MDCN_MAXDG || (a.C % (8 * a.DG)) || a.omc < 3 * K * a.DG)
         return (int)hipErrorInvalidValue;
-    const int cpg = (a.C >> 3) / a.DG;
-    if (cpg & (cpg - 1)) return (int)hipErrorInvalidValue;      // lane-segment reduction wants a power of two
     if ((long)a.B * a.IH * a.IW > 0x7fffffffL) return (int)hipErrorInvalidValue;
     return 0;
 }
@@ -684,28 +691,94 @@ static bool mdcn_tiling(int B, int C, int OH, int OW, int kh, int kw, int stride
     return true;
 }
 
-LOFT_EXPORT int64_t loft_mdcn_bwd_workspace_bytes(int B, int C, int OH, int OW, int kh, int kw, int stride, int dil,
-                                                  int deform_groups, int offmask_stride) {
+// The form a backward launch takes.  LOFT_MDCN_AUTO: the shipped rule (a tiled kernel wherever mdcn_tiling applies: fp32 ->
+// window kernel, 16-bit -> binned kernel; else the generic kernel), with mdcn_tiling's split / slab counts.  A forced family
+// (tests, A/B timing) keeps mdcn_tiling's tile geometry and takes its split count / channels per lane from bits 8-15 of
+// `variant` (0: the rule's own); what the operands cannot take is hipErrorInvalidValue.  dtype < 0: not known (the workspace
+// query) -- a forced family implies it, AUTO sizes for both.
+static int mdcn_plan(const MdcnArgs& a, int dtype, int variant, int* family, MdcnTiling* t) {
+    const int fam = variant & 0xff, n = (variant >> 8) & 0xff;
+    if (variant < 0 || (variant >> 16) || fam > LOFT_MDCN_BWD_BIN || (fam <= LOFT_MDCN_BWD_GENERIC && n))
+        return (int)hipErrorInvalidValue;
+    if (int e = mdcn_check(a)) return e;
+    if (a.M <= 0) { *family = LOFT_MDCN_BWD_GENERIC; return 0; }      // nothing is launched
+    const bool tiled = mdcn_tiling(a.B, a.C, a.OH, a.OW, a.kh, a.kw, a.stride, a.dil, a.DG, a.omc, t);
+    if (fam == LOFT_MDCN_AUTO) {
+        *family = !tiled ? LOFT_MDCN_BWD_GENERIC : (dtype == LOFT_F32 ? LOFT_MDCN_BWD_TILE : LOFT_MDCN_BWD_BIN);
+        return 0;
+    }
+    *family = fam;
+    if (fam == LOFT_MDCN_BWD_GENERIC) return 0;
+    if (!tiled) return (int)hipErrorInvalidValue;               // deform groups, dilation, C % 64, window over 15 x 15
+    const int nchunks = a.C / 64;
+    int parts;
+    if (fam == LOFT_MDCN_BWD_TILE) {
+        if (dtype >= 0 && dtype != LOFT_F32) return (int)hipErrorInvalidValue;
+        if (n > nchunks) return (int)hipErrorInvalidValue;
+        if (n) t->splits = n;
+        parts = t->splits;
+    } else {
+        if (dtype >= 0 && dtype != LOFT_ACT16) return (int)hipErrorInvalidValue;
+        if (n && ((n != 1 && n != 2 && n != 4 && n != 8) || nchunks % n)) return (int)hipErrorInvalidValue;
+        if (n) t->cpl = n;
+        t->nslab = nchunks / t->cpl;
+        parts = t->nslab;
+    }
+    t->domp_floats = parts > 1 ? (long)parts * a.M * a.omc : 0;
+    return 0;
+}
+
+LOFT_EXPORT int64_t loft_mdcn_bwd_workspace_bytes_v(int B, int C, int OH, int OW, int kh, int kw, int stride, int dil,
+                                                    int deform_groups, int offmask_stride, int variant) {
+    // (IH, IW, pad do not enter the tiling; mdcn_check's pixel-count limit is the launch's to report)
+    MdcnArgs a{B, 1, 1, C, OH, OW, kh, kw, stride, 0, dil, deform_groups, offmask_stride, (long)B * OH * OW};
     MdcnTiling t;
-    if (!mdcn_tiling(B, C, OH, OW, kh, kw, stride, dil, deform_groups, offmask_stride, &t)) return 0;
+    int family;
+    if ((variant & 0xff) == LOFT_MDCN_AUTO && !(variant >> 8)) {   // today's answer, also for shapes the launch would refuse
+        if (!mdcn_tiling(B, C, OH, OW, kh, kw, stride, dil, deform_groups, offmask_stride, &t)) return 0;
+    } else {
+        if (int e = mdcn_plan(a, -1, variant, &family, &t)) return -(int64_t)e;
+        if (family == LOFT_MDCN_BWD_GENERIC) return 0;
+    }
     return (int64_t)(t.win_floats + t.domp_floats) * (int64_t)sizeof(float);
 }
 
-LOFT_EXPORT int loft_mdcn_sample_bwd(const void* x, const float* offmask, const void* dcol, float* dx, float* doffmask,
-                                     int dtype, int B, int IH, int IW, int C, int OH, int OW, int kh, int kw, int stride,
-                                     int pad, int dil, int deform_groups, int offmask_stride, void* workspace,
-                                     void* stream) {
+LOFT_EXPORT int64_t loft_mdcn_bwd_workspace_bytes(int B, int C, int OH, int OW, int kh, int kw, int stride, int dil,
+                                                  int deform_groups, int offmask_stride) {
+    return loft_mdcn_bwd_workspace_bytes_v(B, C, OH, OW, kh, kw, stride, dil, deform_groups, offmask_stride, LOFT_MDCN_AUTO);
+}
+
+LOFT_EXPORT int loft_mdcn_bwd_form(int B, int IH, int IW, int C, int OH, int OW, int kh, int kw, int stride, int pad, int dil,
+                                   int deform_groups, int offmask_stride, int dtype, int variant) {
+    if (dtype != LOFT_F32 && dtype != LOFT_ACT16) return -(int)hipErrorInvalidValue;
+    MdcnArgs a{B, IH, IW, C, OH, OW, kh, kw, stride, pad, dil, deform_groups, offmask_stride, (long)B * OH * OW};
+    MdcnTiling t;
+    int family;
+    if (int e = mdcn_plan(a, dtype, variant, &family, &t)) return -e;
+    if (family == LOFT_MDCN_BWD_GENERIC) return family;
+    return family | ((family == LOFT_MDCN_BWD_TILE ? t.splits : t.cpl) << 8) | (t.TH << 16);
+}
+
+LOFT_EXPORT int loft_mdcn_sample_bwd_v(const void* x, const float* offmask, const void* dcol, float* dx, float* doffmask,
+                                       int dtype, int B, int IH, int IW, int C, int OH, int OW, int kh, int kw, int stride,
+                                       int pad, int dil, int deform_groups, int offmask_stride, void* workspace, int variant,
+                                       void* stream) {
     if (dtype != LOFT_F32 && dtype != LOFT_ACT16) return (int)hipErrorInvalidValue;   // the other build's 16-bit type
     MdcnArgs a{B, IH, IW, C, OH, OW, kh, kw, stride, pad, dil, deform_groups, offmask_stride, (long)B * OH * OW};
-    if (int e = mdcn_check(a)) return e;
-    if (a.M <= 0) return 0;
     MdcnTiling t;
-    if (workspace && mdcn_tiling(B, C, OH, OW, kh, kw, stride, dil, deform_groups, offmask_stride, &t)) {
+    int family;
+    if (int e = mdcn_plan(a, dtype, variant, &family, &t)) return e;
+    if (!workspace) {                                           // AUTO: the generic kernel; a tiled form cannot run without one
+        if ((variant & 0xff) != LOFT_MDCN_AUTO && family != LOFT_MDCN_BWD_GENERIC) return (int)hipErrorInvalidValue;
+        family = LOFT_MDCN_BWD_GENERIC;
+    }
+    if (a.M <= 0) return 0;
+    if (family != LOFT_MDCN_BWD_GENERIC) {
         const unsigned ntiles = (unsigned)(t.tiles_x * t.tiles_y * B);
         float* ws = (float*)workspace;
         float* domp = ws + t.win_floats;
         int parts = t.splits;
-        if (dtype == LOFT_F32)
+        if (family == LOFT_MDCN_BWD_TILE)
             hipLaunchKernelGGL(mdcn_sample_bwd_tile_kernel<float>, dim3(ntiles, t.splits), dim3(512), 0, (hipStream_t)stream,
                                (const float*)x, offmask, (const float*)dcol, dx, doffmask, a, t.TH, t.TW, t.tiles_x, t.tiles_y, ws,
                                domp);
@@ -747,4 +820,12 @@ LOFT_EXPORT int loft_mdcn_sample_bwd(const void* x, const float* offmask, const 
                            (const bf16_t*)dcol, dx, doffmask, a);
     LOFT_LAUNCH_CHECK();
     return 0;
+}
+
+LOFT_EXPORT int loft_mdcn_sample_bwd(const void* x, const float* offmask, const void* dcol, float* dx, float* doffmask,
+                                     int dtype, int B, int IH, int IW, int C, int OH, int OW, int kh, int kw, int stride,
+                                     int pad, int dil, int deform_groups, int offmask_stride, void* workspace,
+                                     void* stream) {
+    return loft_mdcn_sample_bwd_v(x, offmask, dcol, dx, doffmask, dtype, B, IH, IW, C, OH, OW, kh, kw, stride, pad, dil,
+                                  deform_groups, offmask_stride, workspace, LOFT_MDCN_AUTO, stream);
 }

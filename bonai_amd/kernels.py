@@ -2045,8 +2045,31 @@ def mdcn_sample_fwd(x, om, kh, kw, stride=1, pad=0, dil=1, deform_groups=1):
     return col
 
 
-def mdcn_sample_bwd(x, om, dcol, kh, kw, stride=1, pad=0, dil=1, deform_groups=1):
-    """-> (dx fp32 [B,C,IH,IW] channels_last, dom fp32 like om)."""
+# LOFT_MDCN_*: the kernel family of the sampling backward (mdcn_sample_bwd(variant=...), mdcn_bwd_form)
+MDCN_AUTO, MDCN_BWD_GENERIC, MDCN_BWD_TILE, MDCN_BWD_BIN = 0, 1, 2, 3
+
+
+def mdcn_variant(family, count=0):
+    """LOFT_MDCN_VARIANT: a family with its split count (window kernel) / channels per lane (binned kernel); 0 = AUTO's own."""
+    return int(family) | (int(count) << 8)
+
+
+def mdcn_bwd_form(B, IH, IW, C, OH, OW, kh, kw, stride=1, pad=0, dil=1, deform_groups=1, omc=None, dtype=torch.float32,
+                  variant=MDCN_AUTO):
+    """-> (family, count, tile edge) of the kernel mdcn_sample_bwd launches for operands of this shape and dtype (MDCN_BWD_*; count:
+    splits of the window kernel / channels per lane of the binned kernel).  Asks the library's launch path (loft_mdcn_bwd_form);
+    touches no device.  Raises for arguments the launch rejects."""
+    lib = L.load()
+    if omc is None:
+        omc = 3 * deform_groups * kh * kw
+    f = lib.loft_mdcn_bwd_form(B, IH, IW, C, OH, OW, kh, kw, stride, pad, dil, deform_groups, omc, L._DT[dtype], int(variant))
+    if f < 0:
+        L.check(-f, 'loft_mdcn_bwd_form')
+    return f & 0xff, (f >> 8) & 0xff, f >> 16
+
+
+def mdcn_sample_bwd(x, om, dcol, kh, kw, stride=1, pad=0, dil=1, deform_groups=1, variant=MDCN_AUTO):
+    """-> (dx fp32 [B,C,IH,IW] channels_last, dom fp32 like om).  variant: MDCN_AUTO or a forced kernel (mdcn_variant)."""
     lib = L.load()
     L.dev_check(x, om, dcol)
     x, om, dcol = _nhwc(x), _nhwc(om), _nhwc(dcol)
@@ -2054,13 +2077,15 @@ def mdcn_sample_bwd(x, om, dcol, kh, kw, stride=1, pad=0, dil=1, deform_groups=1
         raise L.LoftHipError('dcol must have the dtype of x')
     B, C, IH, IW = x.shape
     _, omc, OH, OW = om.shape
+    nws = lib.loft_mdcn_bwd_workspace_bytes_v(B, C, OH, OW, kh, kw, stride, dil, deform_groups, omc, int(variant))
+    if nws < 0:
+        L.check(-nws, 'loft_mdcn_bwd_workspace_bytes_v')
     dx = zeros_nhwc(B, C, IH, IW, torch.float32, x.device)
     dom = zeros_nhwc(B, omc, OH, OW, torch.float32, x.device)
-    nws = lib.loft_mdcn_bwd_workspace_bytes(B, C, OH, OW, kh, kw, stride, dil, deform_groups, omc)
     ws = torch.empty(nws, dtype=torch.uint8, device=x.device) if nws > 0 else None
-    L.check(lib.loft_mdcn_sample_bwd(L.ptr(x), L.ptr(om), L.ptr(dcol), L.ptr(dx), L.ptr(dom), L.dtype_code(x), B, IH, IW, C,
-                                     OH, OW, kh, kw, stride, pad, dil, deform_groups, omc, L.ptr(ws), L.stream()),
-            'loft_mdcn_sample_bwd')
+    L.check(lib.loft_mdcn_sample_bwd_v(L.ptr(x), L.ptr(om), L.ptr(dcol), L.ptr(dx), L.ptr(dom), L.dtype_code(x), B, IH, IW, C,
+                                       OH, OW, kh, kw, stride, pad, dil, deform_groups, omc, L.ptr(ws), int(variant), L.stream()),
+            'loft_mdcn_sample_bwd_v')
     return dx, dom
 
 

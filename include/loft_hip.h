@@ -743,7 +743,7 @@ int loft_stem7x7_pool_wgrad(const float* img, const void* y, const void* gp, flo
  * sigmoid applied here).  col: [B*OH*OW][K][C] (same dtype as x) = mask * zero-padded bilinear sample, i.e. the A operand of
  * the 1x1 contraction with the weight packed as [Cout][K*C] that loft_conv_tap_* then runs.
  * bwd: dcol (layout of col) -> dx fp32 [B,IH,IW,C] (ACCUMULATED with atomics: caller zeroes), doffmask fp32 (layout of offmask;
- * channels >= 3*DG*K untouched).  K = kh*kw <= 9, DG <= 4, C % (8*DG) == 0 and C/(8*DG) a power of two.
+ * channels >= 3*DG*K untouched).  K = kh*kw <= 9, DG <= 4, C % (8*DG) == 0.
  * workspace: loft_mdcn_bwd_workspace_bytes() bytes; 0 / NULL = the generic kernel that scatters with global fp32 atomics
  * (deform_groups > 1, C % 64 != 0).  With a workspace the tiled, atomic-free path runs (LDS gradient windows per output
  * tile, stored to the workspace and summed per input pixel by a second pass; doffmask is fully overwritten). */
@@ -755,6 +755,34 @@ int loft_mdcn_sample_bwd(const void* x, const float* offmask, const void* dcol, 
                          int deform_groups, int offmask_stride, void* workspace, void* stream);
 int64_t loft_mdcn_bwd_workspace_bytes(int B, int C, int OH, int OW, int kh, int kw, int stride, int dil, int deform_groups,
                                       int offmask_stride);
+/* The backward with the kernel family chosen by the caller (tests / A-B timing).  variant = a family code, and in bits 8-15 the
+ * family's count (LOFT_MDCN_VARIANT): the channel splits of the window kernel (1 .. C/64: gridDim.y, a workgroup walks every
+ * splits-th 64-channel chunk) or the channels per lane of the binned kernel (1, 2, 4, 8 and a divisor of C/64; C/(64*CPL) slabs
+ * ride on gridDim.y); 0 = the count LOFT_MDCN_AUTO's rule gives this shape.  LOFT_MDCN_AUTO = loft_mdcn_sample_bwd: a tiled
+ * kernel when a workspace is given, deform_groups == 1, C % 64 == 0, dil == 1 and the tile window fits 15 x 15 (fp32: window
+ * kernel, 16-bit: binned kernel), else the generic kernel; counts lowered until about 1024 workgroups exist.
+ * A forced form the operands cannot take is hipErrorInvalidValue and launches nothing: the binned kernel on fp32, the window
+ * kernel on the 16-bit type, a CPL that is no divisor of C/64, a tiled family where AUTO's conditions on deform_groups, dil, C
+ * or the window fail or without a workspace, splits outside 1 .. C/64, a count with AUTO / GENERIC, an unknown code. */
+#define LOFT_MDCN_AUTO 0
+#define LOFT_MDCN_BWD_GENERIC 1   /* mdcn_sample_bwd_kernel<T>: global fp32 atomics, any deform_groups (needs no workspace) */
+#define LOFT_MDCN_BWD_TILE 2      /* mdcn_sample_bwd_tile_kernel<float>: fp32 LDS window per output tile */
+#define LOFT_MDCN_BWD_BIN 3       /* mdcn_sample_bwd_bin_kernel<CPL>: 16-bit, contributions binned per window pixel */
+#define LOFT_MDCN_VARIANT(family, count) ((family) | ((count) << 8))
+int loft_mdcn_sample_bwd_v(const void* x, const float* offmask, const void* dcol, float* dx, float* doffmask, int dtype, int B,
+                           int IH, int IW, int C, int OH, int OW, int kh, int kw, int stride, int pad, int dil,
+                           int deform_groups, int offmask_stride, void* workspace, int variant, void* stream);
+/* Workspace bytes of loft_mdcn_sample_bwd_v for `variant` (the partial doffmask buffers scale with the forced split / slab
+ * count); LOFT_MDCN_AUTO: loft_mdcn_bwd_workspace_bytes, which covers either operand type.  < 0: -hipError_t (a forced form
+ * the shape cannot take). */
+int64_t loft_mdcn_bwd_workspace_bytes_v(int B, int C, int OH, int OW, int kh, int kw, int stride, int dil, int deform_groups,
+                                        int offmask_stride, int variant);
+/* Which kernel loft_mdcn_sample_bwd_v launches for these arguments when it is given a workspace: the launch's own decision,
+ * host only -- no device is touched.  -> family | count << 8 | tile edge << 16 (family: LOFT_MDCN_BWD_*; count: splits of the
+ * window kernel / CPL of the binned kernel; tile edge: 8 or 4 output pixels; both 0 for the generic kernel), or -hipError_t for
+ * arguments the launch rejects. */
+int loft_mdcn_bwd_form(int B, int IH, int IW, int C, int OH, int OW, int kh, int kw, int stride, int pad, int dil,
+                       int deform_groups, int offmask_stride, int dtype, int variant);
 
 /* ---- weight fold + pack -----------------------------------------------------------------------------
  * Per conv and step: fp32 master weight [Cout][Cin][R][S] (the reference/checkpoint layout) -> bf16 operand packings
