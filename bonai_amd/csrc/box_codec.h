@@ -3,6 +3,7 @@
 // with -ffp-contract=off, so a row decodes to the same bits in either).
 #pragma once
 #include "loft_common.h"
+#include "../../include/loft_hip.h"
 
 // ---- DeltaXYWHBBoxCoder.decode (delta_xywh_bbox_coder.py:118-204) ------------------------------------------------------------------
 __device__ __forceinline__ float4 decode_box(const float4 r, float d0, float d1, float d2, float d3, const float* means,
@@ -82,3 +83,24 @@ __device__ __forceinline__ float paste_sample(int x, int y, const float4 b, int 
     return v;
 }
 __device__ __forceinline__ float paste_sigmoid(float logit) { return 1.f / (1.f + expf(-logit)); }
+// the merged taps of one detection, staged by the whole workgroup (aug_test_mask + merge_aug_masks, test_mixins.py:179-208): tap
+// (r, c) = the sequential fp32 sum, in view order, of sigmoid(logit) read through each view's inverse permutation of the S x S grid
+// (LOFT_D4_*: original tap (r, c) is the view's tap (y, x), (y', x') = T ? (c, r) : (r, c), then the mirrors), divided by V.
+// logits [V,N,S,S]; taps: S*S floats of LDS; the caller synchronises before reading them.  V == 1 with the identity element
+// leaves paste_sigmoid(logit), bit for bit.
+__device__ __forceinline__ void paste_stage_taps(float* taps, const float* __restrict__ logits, int n, int N, int V, int S,
+                                                 const int32_t* __restrict__ views) {
+    const int SS = S * S;
+    for (int k = threadIdx.x; k < SS; k += blockDim.x) {
+        const int r = k / S, c = k - r * S;
+        float acc = 0.f;
+        for (int v = 0; v < V; ++v) {
+            const int e = views[v] & LOFT_D4_ELEMENT_MASK;
+            int yv = (e & LOFT_D4_TRANSPOSE) ? c : r, xv = (e & LOFT_D4_TRANSPOSE) ? r : c;
+            if (e & LOFT_D4_MIRROR_X) xv = S - 1 - xv;
+            if (e & LOFT_D4_MIRROR_Y) yv = S - 1 - yv;
+            acc += paste_sigmoid(logits[((long)v * N + n) * SS + yv * S + xv]);
+        }
+        taps[k] = acc / (float)V;
+    }
+}

@@ -218,19 +218,7 @@ __global__ __launch_bounds__(256) void mask_paste_views_kernel(const float* __re
         }
         return;
     }
-    const int SS = S * S;
-    for (int k = threadIdx.x; k < SS; k += blockDim.x) {
-        const int r = k / S, c = k - r * S;
-        float acc = 0.f;
-        for (int v = 0; v < V; ++v) {
-            const int e = views[v] & LOFT_D4_ELEMENT_MASK;
-            int yv = (e & LOFT_D4_TRANSPOSE) ? c : r, xv = (e & LOFT_D4_TRANSPOSE) ? r : c;
-            if (e & LOFT_D4_MIRROR_X) xv = S - 1 - xv;
-            if (e & LOFT_D4_MIRROR_Y) yv = S - 1 - yv;
-            acc += paste_sigmoid(logits[((long)v * N + n) * SS + yv * S + xv]);
-        }
-        taps[k] = acc / (float)V;
-    }
+    paste_stage_taps(taps, logits, n, N, V, S, views);
     __syncthreads();
     auto at = [&](int yy, int xx) -> float {
         if (yy < 0 || yy >= S || xx < 0 || xx >= S) return 0.f;

@@ -1810,6 +1810,59 @@ def mask_paste_views(logits, boxes, views, img_h, img_w, thr=0.5):
     return out
 
 
+_RLE_IDENTITY = {}
+
+
+def mask_paste_rle(logits, boxes, img_h, img_w, thr=0.5, views=None, offsets=None, capacity=None):
+    """The COCO RLE dicts of the pasted masks, from the logits (csrc/mask_rle.hip): logits fp32 [N,S,S], or [V,N,S,S] with ``views``
+    (the device table of tta_view_table), boxes [N,4] in the original frame -> list of N ``{'size': [img_h, img_w], 'counts': bytes}``,
+    equal to ``rle.rle_encode_masks(mask_paste(...))`` / ``(mask_paste_views(...))`` without the [N,img_h,img_w] bitmaps.
+    ``offsets`` fp32 [N,2] (device): the footprints instead, i.e. the strings of ``mask_translate(pasted, offsets)``.
+    Device memory: run positions and string bytes only.  ``capacity`` = (positions, bytes): the kernel's two buffers, read back
+    with the sizes in ONE copy; None: a default that fits building-sized masks, sizes read first and then exactly the bytes used.
+    Buffers that turn out too small are reported by the kernel (nothing is written past them) and the call is repeated once with
+    the sizes it asks for."""
+    lib = L.load()
+    L.dev_check(logits, boxes, views, offsets)
+    logits = logits.float().contiguous()
+    if logits.dim() == 3:
+        logits = logits[None]
+    V, N, S = logits.shape[0], logits.shape[1], logits.shape[-1]
+    img_h, img_w = int(img_h), int(img_w)
+    if N == 0:
+        return []
+    boxes = boxes[:, :4].float().contiguous()
+    dev = logits.device
+    if views is None:
+        if V != 1:
+            raise L.LoftHipError(f'mask_paste_rle: logits of {V} views need their view table')
+        views = _RLE_IDENTITY.get(dev)
+        if views is None:
+            views = _RLE_IDENTITY[dev] = tta_view_table([0], dev)
+    if offsets is not None:
+        offsets = offsets.float().contiguous()
+        if offsets.shape != (N, 2):
+            raise L.LoftHipError(f'mask_paste_rle: offsets [{N},2] expected, got {tuple(offsets.shape)}')
+    one_read = capacity is not None
+    run_cap, byte_cap = (int(capacity[0]), int(capacity[1])) if one_read else (65536 + 1024 * N, 2 * (65536 + 1024 * N))
+    head = 8 * (4 + 2 * N)
+    for attempt in range(2):
+        runs = torch.empty(max(run_cap, 1), dtype=torch.int32, device=dev)
+        buf = torch.empty(head + max(byte_cap, 1), dtype=torch.uint8, device=dev)          # [meta int64 | strings]
+        L.check(lib.loft_mask_rle(L.ptr(logits), L.ptr(boxes), L.ptr(offsets), N, V, S, L.ptr(views), img_h, img_w, thr, L.ptr(runs),
+                                  run_cap, buf.data_ptr() + head, byte_cap, L.ptr(buf), L.stream()), 'loft_mask_rle')
+        host = (buf if one_read else buf[:head]).cpu().numpy()
+        meta = host[:head].view(np.int64)
+        if not meta[2]:
+            break
+        run_cap, byte_cap = int(meta[0]), int(meta[1])
+    else:
+        raise L.LoftHipError(f'loft_mask_rle asked for {run_cap} positions / {byte_cap} bytes and did not fit them')
+    payload = (host[head:head + int(meta[1])] if one_read else buf[head:head + int(meta[1])].cpu().numpy()).tobytes()
+    size = [img_h, img_w]
+    return [{'size': list(size), 'counts': payload[o:o + n]} for o, n in zip(meta[4::2].tolist(), meta[5::2].tolist())]
+
+
 def mask_translate(masks, offsets):
     """Footprints from roofs: masks uint8/bool [N,H,W], offsets fp32 [N,2] = (dx, dy) footprint -> roof (the model's offset
     output) -> uint8 [N,H,W] with out[n, y, x] = masks[n, y + round(dy), x + round(dx)], zero outside the image."""

@@ -380,15 +380,14 @@ class OffsetHeadExpandFeature(_OffsetBase):
             raise NotImplementedError(model)
         return val * torch.where(b[0] > 0, torch.ones_like(b[0]), -torch.ones_like(b[0]))
 
-    def get_offsets(self, offset_pred, det_bboxes, scale_factor=None, rescale=False, img_shape=(1024, 1024)):
-        return K.foa_fuse_decode(self._as_four(offset_pred), det_bboxes, self.offset_coder.stds,
-                                 img_shape).cpu().numpy().astype(np.float32)
+    def get_offsets(self, offset_pred, det_bboxes, scale_factor=None, rescale=False, img_shape=(1024, 1024), with_device=False):
+        return _offsets_out(K.foa_fuse_decode(self._as_four(offset_pred), det_bboxes, self.offset_coder.stds, img_shape), with_device)
 
-    def merge_view_offsets(self, offset_pred, view_rois, V, table, img_shape=(1024, 1024)):
+    def merge_view_offsets(self, offset_pred, view_rois, V, table, img_shape=(1024, 1024), with_device=False):
         """Test-time augmentation: the head's output for the view-major RoIs [V n,5] -> np.float32 [n,2] in the original frame --
         get_offsets per view, the vector mapped back, mean over the views, one launch."""
-        return K.tta_merge_offsets(self._as_four(offset_pred), view_rois, V, table, stds=self.offset_coder.stds, max_shape=img_shape,
-                                   foa=True).cpu().numpy().astype(np.float32)
+        return _offsets_out(K.tta_merge_offsets(self._as_four(offset_pred), view_rois, V, table, stds=self.offset_coder.stds,
+                                                max_shape=img_shape, foa=True), with_device)
 
 
 @HEADS.register_module()
@@ -428,16 +427,37 @@ class OffsetHead(_OffsetBase):
             return t if self.reg_num == 2 else torch.stack([t[:, 0], torch.cos(t[:, 1]), torch.sin(t[:, 1])], -1)
         return K.offset_targets(pos_bboxes, pos_gt_offsets, self.offset_coder.means, self.offset_coder.stds, self.reg_num)
 
-    def get_offsets(self, offset_pred, det_bboxes, scale_factor=None, rescale=False, img_shape=(1024, 1024)):
+    def get_offsets(self, offset_pred, det_bboxes, scale_factor=None, rescale=False, img_shape=(1024, 1024), with_device=False):
         """offset_head.py:190-243 -> np.float32 [n,2] (pixels of the network input; scale_factor is ignored there too)."""
         o = K.offset_decode(offset_pred, det_bboxes, self.offset_coder.means, self.offset_coder.stds, img_shape,
                             polar=self.offset_coordinate == 'polar')
-        return o.cpu().numpy().astype(np.float32)
+        return _offsets_out(o, with_device)
 
-    def merge_view_offsets(self, offset_pred, view_rois, V, table, img_shape=(1024, 1024)):
+    def merge_view_offsets(self, offset_pred, view_rois, V, table, img_shape=(1024, 1024), with_device=False):
         """Test-time augmentation: see OffsetHeadExpandFeature.merge_view_offsets; offset_decode per view."""
-        return K.tta_merge_offsets(offset_pred, view_rois, V, table, self.offset_coder.means, self.offset_coder.stds, img_shape,
-                                   foa=False, polar=self.offset_coordinate == 'polar').cpu().numpy().astype(np.float32)
+        return _offsets_out(K.tta_merge_offsets(offset_pred, view_rois, V, table, self.offset_coder.means, self.offset_coder.stds,
+                                                img_shape, foa=False, polar=self.offset_coordinate == 'polar'), with_device)
+
+
+def _offsets_out(o, with_device):
+    """Decoded offsets [n,2] on the device -> np.float32 [n,2]; ``with_device``: (that, the fp32 device tensor it was copied from) --
+    the fused footprint encoding reads the offsets where they are."""
+    o = o.float()
+    host = o.cpu().numpy().astype(np.float32)
+    return (host, o) if with_device else host
+
+
+def _result_mode(cfg):
+    """(fused, footprints) of test_cfg.rcnn: ``rle_masks='fused'`` encodes the strings from the logits (kernels.mask_paste_rle) and
+    builds no bitmap, so it cannot serve ``keep_device_masks``; ``footprint_rle`` adds the footprints' strings and needs it."""
+    fused = cfg.get('rle_masks', False) == 'fused'
+    footprints = bool(cfg.get('footprint_rle', False))
+    if fused and cfg.get('keep_device_masks', False):
+        raise ValueError("test_cfg.rcnn: rle_masks='fused' builds no bitmaps, keep_device_masks (evaluation) needs them: "
+                         'use rle_masks=True')
+    if footprints and not fused:
+        raise ValueError("test_cfg.rcnn: footprint_rle=True needs rle_masks='fused'")
+    return fused, footprints
 
 
 def _masks_to_device(gt_masks, device):
@@ -664,7 +684,9 @@ class LoftRoIHead(nn.Module):
     @torch.no_grad()
     def simple_test(self, x, proposal_list, img_metas, proposals=None, rescale=False):
         """loft_roi_head.py:196-227 (+ test_mixins.py:53-72,152-177,213-241): one image ->
-        (bbox_results, segm_results, offset_results) with the reference's types."""
+        (bbox_results, segm_results, offset_results) with the reference's types; with test_cfg.rcnn.footprint_rle a fourth
+        element, the footprints' RLE dicts in segm_results' layout."""
+        fused, footprints = _result_mode(self.test_cfg)
         dev = x[0].device
         if isinstance(proposal_list, (list,)):
             props = proposal_list[0]
@@ -697,7 +719,8 @@ class LoftRoIHead(nn.Module):
             [np.zeros((0, 5), dtype=np.float32) for _ in range(ncls)]
         if det_bboxes.shape[0] == 0:
             segm = [[] for _ in range(ncls)] if self.with_mask else None
-            return bbox_results, segm, [[] for _ in range(2)]
+            empty = (bbox_results, segm, [[] for _ in range(2)])
+            return empty + ([[] for _ in range(ncls)] if self.with_mask else None,) if footprints else empty
         _bboxes = det_bboxes[:, :4] * sf if rescale else det_bboxes[:, :4]
         det_rois = torch.cat([_bboxes.new_zeros(_bboxes.shape[0], 1), _bboxes], 1).contiguous()
         segm_results = None
@@ -711,9 +734,13 @@ class LoftRoIHead(nn.Module):
                 img_h = int(np.round(ori_shape[0] * float(np.asarray(scale_factor).reshape(-1)[1 if np.size(scale_factor) > 1 else 0])))
                 img_w = int(np.round(ori_shape[1] * float(np.asarray(scale_factor).reshape(-1)[0])))
                 pb = _bboxes
-            pasted = K.mask_paste(sel, pb.contiguous(), img_h, img_w, cfg.mask_thr_binary)
+            pasted = None if fused else K.mask_paste(sel, pb.contiguous(), img_h, img_w, cfg.mask_thr_binary)
             segm_results = [[] for _ in range(ncls)]
-            if cfg.get('rle_masks', False):
+            if fused:
+                # the same strings from the logits, no bitmap (csrc/mask_rle.hip)
+                for i, r in enumerate(K.mask_paste_rle(sel, pb, img_h, img_w, cfg.mask_thr_binary)):
+                    segm_results[int(dl[i])].append(r)
+            elif cfg.get('rle_masks', False):
                 # what apis/test.py:59-67 (encode_mask_results) produces from the bool arrays, without moving them to the host:
                 # run boundaries are extracted on the device (bonai_amd.rle)
                 from ..rle import rle_encode_masks
@@ -724,7 +751,15 @@ class LoftRoIHead(nn.Module):
                 for i in range(im.shape[0]):
                     segm_results[int(dl[i])].append(im[i])
         offset_pred = self._offset_forward(x, det_rois)
-        offset_results = self.offset_head.get_offsets(offset_pred, _bboxes.contiguous(), scale_factor, rescale)
+        offset_results = self.offset_head.get_offsets(offset_pred, _bboxes.contiguous(), scale_factor, rescale, with_device=footprints)
+        if footprints:
+            offset_results, dev_offsets = offset_results
+            footprint_results = None
+            if self.with_mask:
+                footprint_results = [[] for _ in range(ncls)]
+                for i, r in enumerate(K.mask_paste_rle(sel, pb, img_h, img_w, cfg.mask_thr_binary, offsets=dev_offsets)):
+                    footprint_results[int(dl[i])].append(r)
+            return bbox_results, segm_results, offset_results, footprint_results
         if cfg.get('keep_device_masks', False):
             # tools/test.py --eval: the pasted roof bitmaps stay on the device for bonai_amd.evaluation (footprints by
             # kernels.mask_translate, IoU pairing) -- next to, not instead of, the result tuple
@@ -740,6 +775,7 @@ class LoftRoIHead(nn.Module):
         extension (StandardRoIHead.aug_test, standard_roi_head.py:264-290, returns none).  Every head runs ONCE over all views -- the
         RoIs of view v carry batch index v -- and the per-view softmax / decode / map back / mean are one launch per result
         (bonai_amd/csrc/tta.hip).  Views have scale factor 1, so ``rescale`` changes nothing."""
+        fused, footprints = _result_mode(self.test_cfg)
         dev = x[0].device
         cfg = self.test_cfg
         V = len(elems)
@@ -762,7 +798,8 @@ class LoftRoIHead(nn.Module):
             [np.zeros((0, 5), dtype=np.float32) for _ in range(ncls)]
         if det_bboxes.shape[0] == 0:
             segm = [[] for _ in range(ncls)] if self.with_mask else None
-            return bbox_results, segm, [[] for _ in range(2)]
+            empty = (bbox_results, segm, [[] for _ in range(2)])
+            return empty + ([[] for _ in range(ncls)] if self.with_mask else None,) if footprints else empty
         nd = det_bboxes.shape[0]
         _bboxes = det_bboxes[:, :4].contiguous()
         det_rois = K.tta_view_rois(_bboxes, table, V, img_h, img_w)
@@ -772,10 +809,14 @@ class LoftRoIHead(nn.Module):
             cls_idx = 0 if self.mask_head.class_agnostic else det_labels.repeat(V)
             sel = mask_pred[torch.arange(mask_pred.shape[0], device=dev), cls_idx]
             ori_h, ori_w = meta['ori_shape'][:2]
-            pasted = K.mask_paste_views(sel.reshape(V, nd, sel.shape[-2], sel.shape[-1]), _bboxes, table, ori_h, ori_w,
-                                        cfg.mask_thr_binary)
+            sel = sel.reshape(V, nd, sel.shape[-2], sel.shape[-1])
+            if not fused:
+                pasted = K.mask_paste_views(sel, _bboxes, table, ori_h, ori_w, cfg.mask_thr_binary)
             segm_results = [[] for _ in range(ncls)]
-            if cfg.get('rle_masks', False):
+            if fused:
+                for i, r in enumerate(K.mask_paste_rle(sel, _bboxes, ori_h, ori_w, cfg.mask_thr_binary, views=table)):
+                    segm_results[int(dl[i])].append(r)
+            elif cfg.get('rle_masks', False):
                 from ..rle import rle_encode_masks
                 for i, r in enumerate(rle_encode_masks(pasted)):
                     segm_results[int(dl[i])].append(r)
@@ -783,7 +824,17 @@ class LoftRoIHead(nn.Module):
                 im = pasted.bool().cpu().numpy()
                 for i in range(im.shape[0]):
                     segm_results[int(dl[i])].append(im[i])
-        offset_results = self.offset_head.merge_view_offsets(self._offset_forward(x, det_rois), det_rois, V, table)
+        offset_results = self.offset_head.merge_view_offsets(self._offset_forward(x, det_rois), det_rois, V, table,
+                                                             with_device=footprints)
+        if footprints:
+            offset_results, dev_offsets = offset_results
+            footprint_results = None
+            if self.with_mask:
+                footprint_results = [[] for _ in range(ncls)]
+                for i, r in enumerate(K.mask_paste_rle(sel, _bboxes, ori_h, ori_w, cfg.mask_thr_binary, views=table,
+                                                       offsets=dev_offsets)):
+                    footprint_results[int(dl[i])].append(r)
+            return bbox_results, segm_results, offset_results, footprint_results
         if cfg.get('keep_device_masks', False):
             self.last_device_masks = pasted
             self.last_dets, self.last_det_labels = db, dl

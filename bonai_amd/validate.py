@@ -21,17 +21,23 @@ def run_dataset(model, ds, evaluate=False, eval_kw=None, log=print, indices=None
     """-> (results as single_gpu_test returns them, per-image evaluation records or None).  ``indices``: the images to run
     (default: all of them, in order)."""
     roi = model.roi_head
-    roi.test_cfg['keep_device_masks'] = True
-    # simple_test encodes the pasted device bitmaps as RLE itself (one pass): without this it also copied every detection's
-    # full-image bool mask to the host (up to 100 x 1 MiB per tile) for a result this loop then threw away (ADVICE round 4)
-    roi.test_cfg['rle_masks'] = True
+    # rle_masks='fused' (tools/test.py --fused-rle / --footprints): strings from the logits, no bitmaps -- nothing to evaluate on
+    fused = roi.test_cfg.get('rle_masks', False) == 'fused'
+    if fused and evaluate:
+        raise ValueError("run_dataset(evaluate=True) pairs buildings on the pasted bitmaps, rle_masks='fused' builds none")
+    if not fused:
+        roi.test_cfg['keep_device_masks'] = True
+        # simple_test encodes the pasted device bitmaps as RLE itself (one pass): without this it also copied every detection's
+        # full-image bool mask to the host (up to 100 x 1 MiB per tile) for a result this loop then threw away (ADVICE round 4)
+        roi.test_cfg['rle_masks'] = True
     results, records = [], ([] if evaluate else None)
     for i, data in (ds.test_batches() if indices is None else ds.test_batches(indices=[int(i) for i in indices])):
         with torch.no_grad():
-            bbox_res, segm, off_res = model(return_loss=False, rescale=True, **data)
+            res = tuple(model(return_loss=False, rescale=True, **data))      # a 4-tuple with test_cfg.rcnn.footprint_rle
+        bbox_res, segm, off_res = res[:3]
         n_det = sum(b.shape[0] for b in bbox_res)
-        pasted = roi.last_device_masks if n_det else None
-        results.append((bbox_res, segm, off_res))
+        pasted = roi.last_device_masks if n_det and not fused else None
+        results.append(res)
         if evaluate:
             h, w = data['img_metas'][0][0]['ori_shape'][:2]
             pm = pasted if pasted is not None else torch.zeros(0, h, w, dtype=torch.uint8, device=data['img'][0].device)

@@ -677,6 +677,21 @@ int loft_tta_merge_offsets(const float* pred, const float* rois, int64_t n, int 
 int loft_mask_paste_views(const float* logits, const float* boxes, int N, int V, int S, const int32_t* views, int img_h, int img_w,
                           float thr, uint8_t* out, void* stream);
 
+/* ---- mask results as COCO RLE strings, from the logits (bonai_amd/csrc/mask_rle.hip) ------------------------------------------------
+ * loft_mask_rle: logits fp32 [V,N,S,S] (class selected, S <= 64), boxes [N,4] in the original frame, views DEVICE int32 [V] of
+ * LOFT_D4_* elements (V == 1 with the identity: simple_test) -> for every detection the bytes of pycocotools' compressed string
+ * (cocoapi rleToString) of the column-major runs of its mask: the string bonai_amd/rle.py makes of loft_mask_paste_views' bitmap,
+ * which is never built -- only the pixels of the box's tight window are evaluated.  offsets NULL: the roof mask; offsets fp32 [N,2]:
+ * the footprint, loft_mask_translate of that roof (footprint(y, x) = roof(y + lroundf(dy), x + lroundf(dx)), 0 outside the image).
+ * runs: DEVICE scratch of run_cap int32 (a detection's run start positions); out: DEVICE, byte_cap bytes (the strings, each in a
+ * segment reserved on an atomic cursor: placement may vary between launches, content does not); meta: DEVICE int64 [4 + 2N],
+ * zeroed here: [0] int32 positions needed, [1] bytes needed, [2] nonzero when a detection did not fit -- nothing is written past a
+ * capacity, and (run_cap, byte_cap) = ([0], [1]) always suffices for a second call -- [4 + 2n], [5 + 2n] = (byte offset, byte length)
+ * of detection n (offset -1: did not fit).  hipErrorInvalidValue for img_h * img_w >= 2^31, N > 65535, S > 64, V > 8 or
+ * img_w > 8192 (one LDS counter per window column). */
+int loft_mask_rle(const float* logits, const float* boxes, const float* offsets, int N, int V, int S, const int32_t* views, int img_h,
+                  int img_w, float thr, void* runs, int64_t run_cap, uint8_t* out, int64_t byte_cap, void* meta, void* stream);
+
 /* ---- sparse backward of the RPN head -------------------------------------------------------------
  * The RPN losses (anchor_head.py:429-497, rpn_head.py:56-80) read the head outputs only at the sampled anchors (<= 256 per
  * image of 261 888), so its backward runs on the selected pixels: level_ptrs/H/W (HOST arrays, n_levels <= 8) describe the

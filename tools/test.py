@@ -2,6 +2,7 @@
 """Entry point with the argv surface of the reference's tools/test.py:17-67 for the LOFT hot path.
 
     python tools/test.py CONFIG [CHECKPOINT] [--out results.pkl] [--eval] [--ann-file F --img-prefix D] [--num N] [--tta h,v,r90]
+                         [--fused-rle] [--footprints]
 
 Dataset mode (the annotation file of ``cfg.data.test`` -- or ``--ann-file`` -- exists): every image of the file goes through
 `model(return_loss=False, rescale=True, img=[...], img_metas=[[...]])` with samples_per_gpu = 1 (apis/test.py:26,53-72), results
@@ -9,6 +10,8 @@ are the reference's 3-tuples (bbox_results, segm_results as COCO RLE, offset_res
 single_gpu_test returns it.  ``--eval`` evaluates on the spot what the reference evaluates from that pickle with
 tools/bonai/bonai_evaluation.py: roof / footprint F1 at IoU 0.5 and the offset aEPE / aAE of the footprint pairs
 (bonai_amd/evaluation.py; footprints = roof bitmaps translated by the predicted offset, on the device).
+``--fused-rle`` encodes the RLE strings straight from the mask logits (bonai_amd/csrc/mask_rle.hip: the same bytes, no full-image
+bitmaps); ``--footprints`` also appends the footprints' RLE dicts (roof read through the rounded offset) as a fourth tuple element.
 Without dataset files (offline, as in this image) or with ``--synthetic`` the inputs are seeded synthetic tiles.
 """
 import argparse
@@ -43,7 +46,19 @@ def main():
     ap.add_argument('--bitmap-masks', action='store_true',
                     help='synthetic mode: full-image bool masks like simple_test; default: COCO RLE dicts, i.e. what the reference\'s '
                          'single_gpu_test hands on after encode_mask_results (apis/test.py:59-67), encoded from the device')
+    ap.add_argument('--fused-rle', action='store_true',
+                    help='COCO RLE strings encoded on the device from the mask logits, without pasting full-image bitmaps (same bytes); '
+                         'not with --eval or --bitmap-masks, which need the bitmaps')
+    ap.add_argument('--footprints', action='store_true',
+                    help='results become 4-tuples: the footprint masks (roof shifted by the rounded offset) as RLE dicts in the layout of '
+                         'the segm results; implies --fused-rle')
     args = ap.parse_args()
+    if args.footprints:
+        args.fused_rle = True
+    if args.fused_rle and args.eval:
+        ap.error('--fused-rle / --footprints build no mask bitmaps, --eval pairs buildings on them: drop one of the two')
+    if args.fused_rle and args.bitmap_masks:
+        ap.error('--fused-rle / --footprints return RLE dicts, --bitmap-masks asks for full-image bool masks: drop one of the two')
     from bonai_amd.config import Config
     from bonai_amd.loft import build_detector
     from bonai_amd.synth import make_batch
@@ -59,6 +74,9 @@ def main():
     dataset_mode = not args.synthetic and files and all(os.path.exists(f) for f in files)
     if not dataset_mode and not args.bitmap_masks:
         cfg.test_cfg.rcnn['rle_masks'] = True
+    if args.fused_rle:
+        cfg.test_cfg.rcnn['rle_masks'] = 'fused'
+        cfg.test_cfg.rcnn['footprint_rle'] = args.footprints
     from bonai_amd import tta
     tile = tuple(tcfg.get('img_scale', (1024, 1024)))[::-1] if dataset_mode else (args.size, args.size)
     views = tta.parse_tta_arg(args.tta, tile) if args.tta else tta.views_from_pipeline(tcfg.get('pipeline'), tile)
