@@ -1921,6 +1921,131 @@ def mask_pair_counts(pm, gm, win, gbox=None, out=None):
     return inter, area_p, area_g
 
 
+# ------------------------------------------------------------------ COCO AP (coco_eval.hip)
+
+COCO_MAX_GT, COCO_MAX_THRS, COCO_MAX_RECS, COCO_TOO_MANY_GT = 4096, 16, 128, -2        # include/loft_hip.h LOFT_COCO_*
+COCO_AREA_RNG = ((0 ** 2, 1e5 ** 2), (0 ** 2, 32 ** 2), (32 ** 2, 96 ** 2), (96 ** 2, 1e5 ** 2))   # cocoeval.py Params.areaRng
+
+
+def _f64(x, device, shape=None):
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.float64)))
+    t = t.to(device=device, dtype=torch.float64).contiguous()
+    return t if shape is None else t.reshape(shape)
+
+
+def _coco_crowd(iscrowd, G, device):
+    t = iscrowd if isinstance(iscrowd, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(iscrowd).reshape(-1) != 0))
+    t = t.to(device=device, dtype=torch.uint8).contiguous()
+    if t.numel() != G:
+        raise L.LoftHipError(f'one iscrowd flag per ground truth expected ({G}), got {t.numel()}')
+    return t
+
+
+def coco_box_iou(dt, gt, iscrowd, device='cuda'):
+    """pycocotools' bbIou (loft_coco_box_iou): dt [D,4], gt [G,4] as xywh float64 (host arrays are uploaded), iscrowd [G]
+    -> float64 [D,G] on the device."""
+    lib = L.load()
+    dt, gt = _f64(dt, device, (-1, 4)), _f64(gt, device, (-1, 4))
+    L.dev_check(dt, gt)
+    D, G = dt.shape[0], gt.shape[0]
+    crowd = _coco_crowd(iscrowd, G, dt.device)
+    out = torch.empty(D, G, dtype=torch.float64, device=dt.device)
+    L.check(lib.loft_coco_box_iou(L.ptr(dt), L.ptr(gt), L.ptr(crowd), D, G, L.ptr(out), L.stream()), 'loft_coco_box_iou')
+    return out
+
+
+def coco_mask_iou(inter, area_p, area_g, iscrowd):
+    """pycocotools' rleIou from mask_pair_counts' int32 device results (loft_coco_mask_iou) -> float64 [D,G] on the device."""
+    lib = L.load()
+    L.dev_check(inter, area_p, area_g)
+    if any(t.dtype != torch.int32 for t in (inter, area_p, area_g)) or inter.dim() != 2 \
+            or tuple(inter.shape) != (area_p.numel(), area_g.numel()):
+        raise L.LoftHipError('coco_mask_iou takes the int32 inter [D,G], area_p [D], area_g [G] of mask_pair_counts')
+    inter, area_p, area_g = inter.contiguous(), area_p.contiguous(), area_g.contiguous()
+    D, G = inter.shape
+    crowd = _coco_crowd(iscrowd, G, inter.device)
+    out = torch.empty(D, G, dtype=torch.float64, device=inter.device)
+    L.check(lib.loft_coco_mask_iou(L.ptr(inter), L.ptr(area_p), L.ptr(area_g), L.ptr(crowd), D, G, L.ptr(out), L.stream()),
+            'loft_coco_mask_iou')
+    return out
+
+
+def coco_match(ious, det_counts, gt_counts, det_area, gt_area, gt_crowd, iou_thrs, area_rng=COCO_AREA_RNG):
+    """COCOeval.evaluateImg for a batch of (image, category) segments in one launch (loft_coco_match).
+    ious: float64 device tensor, the segments' row-major [D_s, G_s] IoU matrices one after another (or a list of them);
+    det_counts / gt_counts: host integers per segment; det_area float64 [sum D] (detections in stable descending score order, cut
+    to maxDets[-1]); gt_area float64 / gt_crowd [sum G]; iou_thrs: host float64 values, uploaded as they are.
+    -> (gt_match int32 [sum D, A, T] (-1: unmatched), bits int64 [sum D, 2] (the uint64 words (matched, ignored), bit a*T + t),
+        npig int32 [S, A]), all on the device."""
+    lib = L.load()
+    if isinstance(ious, (list, tuple)):
+        ious = torch.cat([x.reshape(-1) for x in ious]) if ious else None
+    dc, gc = np.asarray(det_counts, np.int64).reshape(-1), np.asarray(gt_counts, np.int64).reshape(-1)
+    S, T, A = dc.size, len(iou_thrs), len(area_rng)
+    if gc.size != S:
+        raise L.LoftHipError(f'coco_match: {S} detection counts and {gc.size} ground-truth counts')
+    if not 1 <= T <= COCO_MAX_THRS or A < 1 or A * T > 64:
+        raise L.LoftHipError(f'coco_match: {A} area ranges x {T} IoU thresholds do not fit the two 64-bit words per detection '
+                             f'(A * T <= 64, T <= {COCO_MAX_THRS})')
+    max_gt = int(gc.max()) if S else 0
+    if max_gt > COCO_MAX_GT:
+        raise L.LoftHipError(f'coco_match: a segment with {max_gt} ground truths; one workgroup holds at most {COCO_MAX_GT}')
+    det_off, gt_off = np.concatenate([[0], np.cumsum(dc)]), np.concatenate([[0], np.cumsum(gc)])
+    iou_off = np.concatenate([[0], np.cumsum(dc * gc)])
+    N, NG = int(det_off[-1]), int(gt_off[-1])
+    dev = det_area.device if isinstance(det_area, torch.Tensor) else (ious.device if ious is not None else torch.device('cuda'))
+    det_area, gt_area = _f64(det_area, dev, (-1,)), _f64(gt_area, dev, (-1,))
+    if ious is None:
+        ious = torch.empty(0, dtype=torch.float64, device=dev)
+    ious = ious.reshape(-1)
+    L.dev_check(ious, det_area, gt_area)
+    if ious.dtype != torch.float64 or ious.numel() != int(iou_off[-1]) or det_area.numel() != N or gt_area.numel() != NG:
+        raise L.LoftHipError(f'coco_match: float64 ious of {int(iou_off[-1])} elements, {N} detection areas and {NG} ground-truth '
+                             f'areas expected, got {ious.dtype} {ious.numel()}, {det_area.numel()}, {gt_area.numel()}')
+    crowd = _coco_crowd(gt_crowd, NG, dev)
+    offs = torch.from_numpy(np.concatenate([iou_off, det_off, gt_off]).astype(np.int64)).to(dev)
+    tabs = _f64(np.concatenate([np.asarray(iou_thrs, np.float64).reshape(-1), np.asarray(area_rng, np.float64).reshape(-1)]), dev)
+    gt_match = torch.empty(N, A, T, dtype=torch.int32, device=dev)
+    det_ign = torch.empty(N, A * T, dtype=torch.uint8, device=dev)
+    bits = torch.empty(N, 2, dtype=torch.int64, device=dev)
+    npig = torch.empty(S, A, dtype=torch.int32, device=dev)
+    code = lib.loft_coco_match(L.ptr(ious.contiguous()), L.ptr(offs), L.ptr(offs[S + 1:]), L.ptr(offs[2 * S + 2:]), L.ptr(det_area),
+                               L.ptr(gt_area), L.ptr(crowd), L.ptr(tabs), L.ptr(tabs[T:]), S, N, max_gt, T, A, L.ptr(gt_match),
+                               L.ptr(det_ign), L.ptr(bits), L.ptr(npig), L.stream())
+    if code == COCO_TOO_MANY_GT:
+        raise L.LoftHipError(f'loft_coco_match: {max_gt} ground truths in one segment, at most {COCO_MAX_GT} fit')
+    L.check(code, 'loft_coco_match')
+    return gt_match, bits, npig
+
+
+def coco_accumulate(scores, bits, rank, npig, max_dets, rec_thrs, T, A=len(COCO_AREA_RNG)):
+    """COCOeval.accumulate for one category (loft_coco_accumulate).  scores float32 [N], bits int64 [N,2], rank int32 [N]: the
+    records of all images in image-id order (host arrays are uploaded); npig [A]: the totals; max_dets, rec_thrs: host values.
+    The global stable descending score sort is segmented_sort_desc with one segment.
+    -> (precision float64 [T,R,A,M], recall float64 [T,A,M]) on the device."""
+    lib = L.load()
+    dev = scores.device if isinstance(scores, torch.Tensor) else torch.device('cuda')
+    up = lambda x, dt: (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))).to(device=dev, dtype=dt).contiguous()
+    scores, bits, rank = up(scores, torch.float32).reshape(-1), up(bits, torch.int64).reshape(-1, 2), up(rank, torch.int32).reshape(-1)
+    L.dev_check(scores)
+    N, M, R = scores.numel(), len(max_dets), len(rec_thrs)
+    if bits.shape[0] != N or rank.numel() != N or len(npig) != A or not 1 <= R <= COCO_MAX_RECS or A * T > 64 or T < 1 or M < 1:
+        raise L.LoftHipError(f'coco_accumulate: {N} scores, {bits.shape[0]} bit pairs, {rank.numel()} ranks, {len(npig)} npig for A={A}, '
+                             f'T={T}, M={M}, R={R} (R <= {COCO_MAX_RECS}, A * T <= 64)')
+    if N:
+        _, perm = segmented_sort_desc(scores, h2d([0, N], torch.int64, dev))
+    else:
+        perm = torch.empty(0, dtype=torch.int32, device=dev)
+    npig_t = up(np.asarray(npig, np.int64).reshape(-1), torch.int64)
+    md = up(np.asarray(max_dets, np.int32).reshape(-1), torch.int32)
+    rt = _f64(np.asarray(rec_thrs, np.float64).reshape(-1), dev)
+    precision = torch.empty(T, R, A, M, dtype=torch.float64, device=dev)
+    recall = torch.empty(T, A, M, dtype=torch.float64, device=dev)
+    L.check(lib.loft_coco_accumulate(L.ptr(bits), L.ptr(rank), L.ptr(perm), N, L.ptr(npig_t), L.ptr(md), L.ptr(rt), T, A, M, R,
+                                     L.ptr(precision), L.ptr(recall), L.stream()), 'loft_coco_accumulate')
+    return precision, recall
+
+
 # ------------------------------------------------------------------ sparse RPN backward helpers
 
 def _sparse_levels(maps):

@@ -921,6 +921,52 @@ int loft_roi_sample_targets(const float* cand, int Ncand, const int64_t* gt_inds
                             float* rois, int64_t* labels, float* label_weights, float* bbox_targets, float* bbox_weights,
                             float* pos_rois, int64_t* pos_img, int64_t* pos_gt, int64_t* pos_row, void* stream);
 
+/* ---- COCO bbox / segm AP on the device (coco_eval.hip) -------------------------------------------------------------------------
+ * COCOeval of the published cocoapi source (PythonAPI/pycocotools/cocoeval.py, common/maskApi.c) restated: what the reference's
+ * CocoDataset.evaluate (mmdet/datasets/coco.py:364-545) runs for metric=['bbox', 'segm'].  [pycocotools not in tree: not run
+ * against it.]  Every deciding operation is fp64 or integer and the file is built with -ffp-contract=off: results are exact.
+ * All pointers are DEVICE pointers.
+ *
+ * loft_coco_box_iou: bbIou.  dt fp64 [D,4], gt fp64 [G,4] as (x, y, w, h), iscrowd uint8 [G] -> out fp64 [D,G]:
+ *   w = min(dx+dw, gx+gw) - max(dx, gx), h likewise, 0 when either is <= 0; i = w*h; u = crowd ? d_area : d_area + g_area - i;
+ *   out = i / u (no "+1").
+ * loft_coco_mask_iou: rleIou from the counts of loft_mask_pair_counts_u8 (inter int32 [D,G], area_p [D], area_g [G]):
+ *   0 when inter == 0, else inter / (crowd ? area_p : area_p + area_g - inter).
+ * D == 0 or G == 0: returns 0 without a launch. */
+int loft_coco_box_iou(const double* dt, const double* gt, const uint8_t* iscrowd, int D, int G, double* out, void* stream);
+int loft_coco_mask_iou(const int* inter, const int* area_p, const int* area_g, const uint8_t* iscrowd, int D, int G, double* out,
+                       void* stream);
+/* loft_coco_match: COCOeval.evaluateImg for S (image, category) segments, all A area ranges and T IoU thresholds in one launch.
+ * Segment s owns detections [det_off[s], det_off[s+1]) -- already in stable descending score order and cut to maxDets[-1] --,
+ * ground truths [gt_off[s], gt_off[s+1]) and the row-major [D_s, G_s] IoU matrix at ious + iou_off[s] (offsets int64 [S+1],
+ * iou_off in elements; IoUs must not be NaN: the two functions above never produce one).  det_area fp64 [total_det], gt_area fp64
+ * and gt_crowd uint8 [total_gt] (iscrowd, which is also the ignore flag: COCOeval._prepare), thrs fp64 [T], area_rng fp64 [A,2]
+ * (bounds inclusive).  Writes, with slot = a*T + t:
+ *   gt_match int32 [total_det, A*T]: index within the segment of the matched ground truth, -1 when unmatched (a matched FLAG, not
+ *     pycocotools' `dtm == 0` test on annotation ids: the two agree whenever no annotation id is 0);
+ *   det_ign uint8 [total_det, A*T]: the matched ground truth's ignore flag, or, unmatched, whether the detection's area is
+ *     outside the range;
+ *   bits uint64 [total_det, 2]: (matched, ignored) of every slot as bit `slot` of the two words;
+ *   npig int32 [S, A]: ground truths that are neither crowd nor outside the range.
+ * max_gt = the largest G_s (the host knows the offsets).  Limits: T <= LOFT_COCO_MAX_THRS, A*T <= 64, and the ground truths of one
+ * segment live in LDS: max_gt > LOFT_COCO_MAX_GT returns LOFT_COCO_TOO_MANY_GT without a launch. */
+#define LOFT_COCO_MAX_GT 4096
+#define LOFT_COCO_MAX_THRS 16
+#define LOFT_COCO_MAX_RECS 128
+#define LOFT_COCO_TOO_MANY_GT (-2)
+int loft_coco_match(const double* ious, const int64_t* iou_off, const int64_t* det_off, const int64_t* gt_off,
+                    const double* det_area, const double* gt_area, const uint8_t* gt_crowd, const double* thrs,
+                    const double* area_rng, int S, int64_t total_det, int max_gt, int T, int A, int32_t* gt_match,
+                    uint8_t* det_ign, uint64_t* bits, int32_t* npig, void* stream);
+/* loft_coco_accumulate: COCOeval.accumulate for one category.  bits uint64 [N,2] / rank int32 [N] (in-image rank) of the N records
+ * of all images in image-id order; perm int32 [N]: their stable descending order by score (loft_segmented_sort_desc, one
+ * segment).  npig int64 [A] (totals over the images), max_dets int32 [M], rec_thrs fp64 [R <= LOFT_COCO_MAX_RECS] exactly as
+ * np.linspace gives them.  -> precision fp64 [T,R,A,M], recall fp64 [T,A,M]; both -1 where npig[a] == 0.  One workgroup per
+ * (t, a, m), none waits on another.  N < 2^31. */
+int loft_coco_accumulate(const uint64_t* bits, const int32_t* rank, const int32_t* perm, int64_t N, const int64_t* npig,
+                         const int32_t* max_dets, const double* rec_thrs, int T, int A, int M, int R, double* precision,
+                         double* recall, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

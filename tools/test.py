@@ -2,7 +2,7 @@
 """Entry point with the argv surface of the reference's tools/test.py:17-67 for the LOFT hot path.
 
     python tools/test.py CONFIG [CHECKPOINT] [--out results.pkl] [--eval] [--ann-file F --img-prefix D] [--num N] [--tta h,v,r90]
-                         [--fused-rle] [--footprints]
+                         [--fused-rle] [--footprints] [--coco-ap]
 
 Dataset mode (the annotation file of ``cfg.data.test`` -- or ``--ann-file`` -- exists): every image of the file goes through
 `model(return_loss=False, rescale=True, img=[...], img_metas=[[...]])` with samples_per_gpu = 1 (apis/test.py:26,53-72), results
@@ -12,6 +12,8 @@ tools/bonai/bonai_evaluation.py: roof / footprint F1 at IoU 0.5 and the offset a
 (bonai_amd/evaluation.py; footprints = roof bitmaps translated by the predicted offset, on the device).
 ``--fused-rle`` encodes the RLE strings straight from the mask logits (bonai_amd/csrc/mask_rle.hip: the same bytes, no full-image
 bitmaps); ``--footprints`` also appends the footprints' RLE dicts (roof read through the rounded offset) as a fourth tuple element.
+``--coco-ap`` (with ``--eval``) adds the COCO bbox / segm AP of CocoDataset.evaluate (bonai_amd/coco_eval.py: COCOeval restated on
+the device, not run against pycocotools): COCOeval.summarize's lines, and the ``bbox_mAP`` ... keys in what ``--eval`` prints.
 Without dataset files (offline, as in this image) or with ``--synthetic`` the inputs are seeded synthetic tiles.
 """
 import argparse
@@ -52,9 +54,16 @@ def main():
     ap.add_argument('--footprints', action='store_true',
                     help='results become 4-tuples: the footprint masks (roof shifted by the rounded offset) as RLE dicts in the layout of '
                          'the segm results; implies --fused-rle')
+    ap.add_argument('--coco-ap', action='store_true',
+                    help='with --eval: COCO bbox / segm AP as the reference\'s CocoDataset.evaluate reports it (needs the pasted '
+                         'bitmaps: not with --fused-rle / --footprints)')
     args = ap.parse_args()
+    if args.coco_ap and not args.eval:
+        ap.error('--coco-ap adds COCO AP to what --eval reports: give --eval too')
     if args.footprints:
         args.fused_rle = True
+    if args.fused_rle and args.coco_ap:
+        ap.error('--coco-ap computes segm AP on the pasted bitmaps, --fused-rle / --footprints build none: drop one of the two')
     if args.fused_rle and args.eval:
         ap.error('--fused-rle / --footprints build no mask bitmaps, --eval pairs buildings on them: drop one of the two')
     if args.fused_rle and args.bitmap_masks:
@@ -93,11 +102,19 @@ def main():
         from bonai_amd.dataset import BonaiDataset
         extra = {k: tcfg[k] for k in ('bbox_type', 'mask_type', 'offset_coordinate', 'resolution', 'classes') if k in tcfg}
         ds = BonaiDataset(ann, prefix, test_mode=True, test_views=views, **extra)
-        results, records = run_dataset(model, ds, evaluate=args.eval, eval_kw=dict(score_thr=args.score_thr, min_area=args.min_area))
+        coco = None
+        if args.coco_ap:
+            from bonai_amd.coco_eval import CocoEvaluator
+            coco = CocoEvaluator(ds, metrics=('bbox', 'segm'))
+        results, records = run_dataset(model, ds, evaluate=args.eval, eval_kw=dict(score_thr=args.score_thr, min_area=args.min_area),
+                                       coco=coco)
         torch.cuda.synchronize()
         print(f'{len(ds) / (time.time() - t0):.2f} img/s (decode + inference + mask paste + RLE' + (' + evaluation)' if args.eval else ')'))
         if args.eval:
-            print(json.dumps(E.summarize(records), indent=1))
+            summary = E.summarize(records)
+            if coco is not None:
+                summary['coco'] = coco.summarize(log=print)
+            print(json.dumps(summary, indent=1))
     else:
         if files and not args.synthetic:
             print(f'dataset files of cfg.data.test not found ({files[:1]}...): synthetic tiles', flush=True)

@@ -12,7 +12,8 @@ reference's batch-dict keys.  Logging mirrors TextLoggerHook's key set (default_
 Validation (the reference's EvalHook, apis/train.py:113-126): when the annotation files of ``cfg.data.val`` -- or ``--val-ann-file``
 -- exist, every ``cfg.evaluation.interval``-th epoch ends with a pass over them (bonai_amd/validate.py: roof / footprint F1 and
 offset aEPE / aAE, sharded over the ranks), an ``Epoch(val)`` line and a line in WORK_DIR/val.log.json; ``evaluation.save_best``
-keeps best.pth.  When batches come from annotation files, ``checkpoint_config.interval`` writes epoch_{E}.pth (a synthetic stream
+keeps best.pth.  ``evaluation.coco_ap=True`` (opt-in) also computes the COCO AP the config's ``metric=['bbox', 'segm']`` names
+(bonai_amd/coco_eval.py): bbox_mAP / segm_mAP in the line, all keys in val.log.json, save_best='coco.segm_mAP'.  When batches come from annotation files, ``checkpoint_config.interval`` writes epoch_{E}.pth (a synthetic stream
 has no epochs of its own: latest.pth only).  Validation runs uncaptured and is refused together with ``--graph``.
 """
 import argparse
@@ -169,7 +170,8 @@ def main():
         vextra = {k: vcfg[k] for k in ('bbox_type', 'mask_type', 'offset_coordinate', 'resolution', 'classes') if k in vcfg}
         vprefix = args.val_img_prefix if args.val_img_prefix is not None else vcfg.get('img_prefix', '')
         validator = Validator(model, BonaiDataset(val_ann, vprefix, test_mode=True, **vextra), score_thr=ev['score_thr'],
-                              min_area=ev['min_area'], iou_thr=ev['iou_thr'], rank=rank, world=world, num=ev['num'])
+                              min_area=ev['min_area'], iou_thr=ev['iou_thr'], rank=rank, world=world, num=ev['num'],
+                              coco=ev.get('coco'))               # evaluation.coco_ap=True: COCO bbox / segm AP next to them
     ckpt_every = int((cfg.get('checkpoint_config') or {}).get('interval', 1) or 0)
     best = dict(value=None, epoch=None)
 
