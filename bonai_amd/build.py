@@ -27,6 +27,7 @@ FLAGS = {
     'augment.hip': ['-ffp-contract=off'],      # Normalize as subtract, then divide: bit for bit the torch chain
     'tta.hip': ['-ffp-contract=off'],          # shares box_codec.h with boxes.hip: a row decodes to the same bits in both
     'mask_rle.hip': ['-ffp-contract=off'],     # the paste rule of box_codec.h again: the same pixels as boxes.hip / tta.hip set
+    'scene.hip': ['-ffp-contract=off'],        # box_codec.h's paste rule and augment.hip's Normalize statement: the same bits
     'coco_eval.hip': ['-ffp-contract=off'],    # COCOeval in fp64: every product, sum and quotient rounded as numpy rounds it
 }
 

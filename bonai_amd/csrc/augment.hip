@@ -12,6 +12,7 @@
 // global memory.  LDS rows are padded by one dword to an ODD dword pitch, so the column walk (lane l on row l) lands on 32
 // different banks.
 #include "loft_common.h"
+#include "image_prep.h"
 #include "../../include/loft_hip.h"
 
 #define D4_TILE 64
@@ -69,15 +70,12 @@ __global__ __launch_bounds__(256) void image_prep_d4_kernel(const uint8_t* __res
     const int ox = threadIdx.x & 63;
     if (ox >= t.tw) return;
     const size_t plane = (size_t)H * W;
+    const PrepNorm nm = {m0, m1, m2, s0, s1, s2};
     for (int oy = threadIdx.x >> 6; oy < t.th; oy += 4) {
         int r, c;
         d4_src(elem, t, ox, oy, r, c);
         const uint8_t* p = bytes + r * (D4_IMG_PITCH * 4) + c * 3;
-        const float v0 = (float)p[keep ? 0 : 2], v1 = (float)p[1], v2 = (float)p[keep ? 2 : 0];
-        float* o = out + (size_t)n * 3 * plane + (size_t)(y0 + oy) * W + x0 + ox;
-        o[0] = (v0 - m0) / s0;
-        o[plane] = (v1 - m1) / s1;
-        o[2 * plane] = (v2 - m2) / s2;
+        prep_store_pixel(p, keep, nm, out + (size_t)n * 3 * plane + (size_t)(y0 + oy) * W + x0 + ox, plane);
     }
 }
 

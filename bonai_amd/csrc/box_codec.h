@@ -62,6 +62,18 @@ __device__ __forceinline__ bool paste_outside(int x, int y, const float4 b, int 
     return (float)x < fmaxf(floorf(b.x) - 1.f, 0.f) || (float)x >= fminf(ceilf(b.z) + 1.f, (float)img_w) ||
            (float)y < fmaxf(floorf(b.y) - 1.f, 0.f) || (float)y >= fminf(ceilf(b.w) + 1.f, (float)img_h);
 }
+// the pixels paste_outside does not exclude, as the integer window [x0, x1) x [y0, y1) (its bounds are whole numbers); empty when
+// x0 >= x1 or y0 >= y1
+struct PasteWin { int x0, x1, y0, y1; };
+__device__ __forceinline__ PasteWin paste_window(const float4 b, int img_h, int img_w) {
+    const float fw = (float)img_w, fh = (float)img_h;
+    PasteWin w;
+    w.x0 = (int)fminf(fmaxf(floorf(b.x) - 1.f, 0.f), fw);
+    w.x1 = (int)fmaxf(fminf(ceilf(b.z) + 1.f, fw), 0.f);
+    w.y0 = (int)fminf(fmaxf(floorf(b.y) - 1.f, 0.f), fh);
+    w.y1 = (int)fmaxf(fminf(ceilf(b.w) + 1.f, fh), 0.f);
+    return w;
+}
 // bilinear grid_sample(align_corners=False, zero padding) of the S x S probabilities at pixel (x, y); at(yy, xx) gives one tap's
 // probability, 0 outside the grid
 template <typename At>

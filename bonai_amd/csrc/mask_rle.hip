@@ -143,11 +143,11 @@ __global__ __launch_bounds__(RLE_THREADS) void mask_rle_kernel(const float* __re
         w.ox = (int)(lx < -img_w ? -img_w : (lx > img_w ? img_w : lx));
         w.oy = (int)(ly < -img_h ? -img_h : (ly > img_h ? img_h : ly));
     }
-    const float fw = (float)img_w, fh = (float)img_h;
-    w.x0 = max((int)fminf(fmaxf(floorf(b.x) - 1.f, 0.f), fw) - w.ox, 0);
-    w.x1 = min((int)fmaxf(fminf(ceilf(b.z) + 1.f, fw), 0.f) - w.ox, img_w);
-    w.y0 = max((int)fminf(fmaxf(floorf(b.y) - 1.f, 0.f), fh) - w.oy, 0);
-    w.y1 = min((int)fmaxf(fminf(ceilf(b.w) + 1.f, fh), 0.f) - w.oy, img_h);
+    const PasteWin roof = paste_window(b, img_h, img_w);
+    w.x0 = max(roof.x0 - w.ox, 0);
+    w.x1 = min(roof.x1 - w.ox, img_w);
+    w.y0 = max(roof.y0 - w.oy, 0);
+    w.y1 = min(roof.y1 - w.oy, img_h);
     auto M = [&](int x, int y) -> bool {
         const int sx = x + w.ox, sy = y + w.oy;
         if (sx < 0 || sx >= img_w || sy < 0 || sy >= img_h) return false;

@@ -1921,6 +1921,90 @@ def mask_pair_counts(pm, gm, win, gbox=None, out=None):
     return inter, area_p, area_g
 
 
+# ------------------------------------------------------------------ whole-scene inference (csrc/scene.hip)
+
+SCENE_MAX_DETS = 65536       # scene.hip SP_MAX_N
+
+
+def scene_tile_prep(scene_u8, origins, tile, channels_kept, mean, std):
+    """loft_scene_tile_prep: scene uint8 [H,W,3] (device), origins int32 [n,2] = (x0, y0) (device), tile = (th, tw) -> fp32
+    [n,3,th,tw]: image_prep_d4's Normalize + HWC -> CHW of the n crops in one launch, exactly 0.0 where a tile leaves the scene."""
+    lib = L.load()
+    L.dev_check(scene_u8, origins)
+    if scene_u8.dtype != torch.uint8 or scene_u8.dim() != 3 or scene_u8.shape[2] != 3 or not scene_u8.is_contiguous():
+        raise L.LoftHipError(f'scene_tile_prep takes a contiguous uint8 [H,W,3] tensor, got {scene_u8.dtype} {tuple(scene_u8.shape)}')
+    if origins.dtype != torch.int32 or origins.dim() != 2 or origins.shape[1] != 2 or not origins.is_contiguous():
+        raise L.LoftHipError(f'scene_tile_prep takes contiguous int32 origins [n,2], got {origins.dtype} {tuple(origins.shape)}')
+    H, W, _ = scene_u8.shape
+    n, (th, tw) = origins.shape[0], (int(tile[0]), int(tile[1]))
+    out = torch.empty(n, 3, th, tw, dtype=torch.float32, device=scene_u8.device)
+    L.check(lib.loft_scene_tile_prep(L.ptr(scene_u8), H, W, L.ptr(origins), n, th, tw, 1 if channels_kept else 0, mean[0], mean[1],
+                                     mean[2], std[0], std[1], std[2], L.ptr(out), L.stream()), 'loft_scene_tile_prep')
+    return out
+
+
+def scene_pair_counts(logits, boxes, tile_idx, img_h, img_w, thr=0.5, capacity=None):
+    """loft_scene_pair_counts: logits fp32 [N,S,S], boxes [N,4] in the scene frame, tile_idx int [N] (device) ->
+    (area int32 [N], records int32 [R,3]): area[i] = the pixel count of mask_paste(logits, boxes, img_h, img_w, thr)[i], and one record
+    (i, j, intersection) with i < j for every pair from different tiles whose paste windows intersect -- in no particular order.
+    No bitmap and no N x N table is built.  ``capacity``: records the buffer holds (None: 16 per detection); a buffer that turns out
+    too small is reported by the kernel (nothing is written past it) and the call is repeated once with the size it asks for."""
+    lib = L.load()
+    L.dev_check(logits, boxes, tile_idx)
+    logits, boxes = logits.float().contiguous(), boxes[:, :4].float().contiguous()
+    tile_idx = tile_idx.to(torch.int32).contiguous()
+    N, S = logits.shape[0], logits.shape[-1]
+    if N > SCENE_MAX_DETS:
+        raise L.LoftHipError(f'scene_pair_counts: {N} detections, at most {SCENE_MAX_DETS} are merged in one call')
+    if logits.dim() != 3 or boxes.shape != (N, 4) or tile_idx.shape != (N,):
+        raise L.LoftHipError(f'scene_pair_counts: logits [N,S,S], boxes [N,4], tile_idx [N] expected, got {tuple(logits.shape)}, '
+                             f'{tuple(boxes.shape)}, {tuple(tile_idx.shape)}')
+    dev = logits.device
+    area = torch.empty(N, dtype=torch.int32, device=dev)
+    cap = 16 * N if capacity is None else int(capacity)
+    for attempt in range(2):
+        recs = torch.empty(max(cap, 1), 3, dtype=torch.int32, device=dev)
+        meta = torch.empty(2, dtype=torch.int64, device=dev)
+        L.check(lib.loft_scene_pair_counts(L.ptr(logits), L.ptr(boxes), L.ptr(tile_idx), N, S, int(img_h), int(img_w), thr, L.ptr(area),
+                                           L.ptr(recs), cap, L.ptr(meta), L.stream()), 'loft_scene_pair_counts')
+        need, short = meta.tolist()
+        if not short:
+            return area, recs[:need]
+        cap = need
+    raise L.LoftHipError(f'loft_scene_pair_counts asked for {cap} records and did not fit them')
+
+
+def scene_suppress(records, area, scores, truncated, merge_thr=0.5):
+    """loft_scene_suppress: records int32 [R,3] and area int32 [N] of scene_pair_counts, scores fp32 [N], truncated bool [N] (device)
+    -> keep uint8 [N]: greedy suppression in priority order (untruncated before truncated, then higher score, then lower index) over
+    the edges inter > merge_thr * min(area_i, area_j).  The rank comes from segmented_sort_desc: the untruncated detections and the
+    truncated ones are its two segments, the score its key, and its stability the index rule."""
+    lib = L.load()
+    L.dev_check(records, area, scores, truncated)
+    N = area.shape[0]
+    dev = area.device
+    keep = torch.empty(N, dtype=torch.uint8, device=dev)
+    if N == 0:
+        return keep
+    records, area = records.to(torch.int32).contiguous(), area.to(torch.int32).contiguous()
+    truncated = truncated.to(torch.bool)
+    if scores.shape != (N,) or truncated.shape != (N,) or records.dim() != 2 or records.shape[1] != 3:
+        raise L.LoftHipError(f'scene_suppress: records [R,3], area / scores / truncated [{N}] expected, got {tuple(records.shape)}, '
+                             f'{tuple(scores.shape)}, {tuple(truncated.shape)}')
+    index = torch.arange(N, dtype=torch.int32, device=dev)
+    by_class = torch.cat([index[~truncated], index[truncated]])              # each class in index order
+    n_whole = N - truncated.sum()
+    seg = torch.stack([torch.zeros_like(n_whole), n_whole, torch.full_like(n_whole, N)]).to(torch.int64)
+    _, order = segmented_sort_desc(scores.float()[by_class.long()], seg, values=by_class)
+    rank = torch.empty(N, dtype=torch.int32, device=dev)
+    rank[order.long()] = index
+    R = records.shape[0]
+    work = torch.empty(3 * N + 2 * R, dtype=torch.int32, device=dev)
+    L.check(lib.loft_scene_suppress(L.ptr(records), R, L.ptr(area), L.ptr(rank), N, float(merge_thr), L.ptr(work), L.ptr(keep),
+                                    L.stream()), 'loft_scene_suppress')
+    return keep
+
+
 # ------------------------------------------------------------------ COCO AP (coco_eval.hip)
 
 COCO_MAX_GT, COCO_MAX_THRS, COCO_MAX_RECS, COCO_TOO_MANY_GT = 4096, 16, 128, -2        # include/loft_hip.h LOFT_COCO_*

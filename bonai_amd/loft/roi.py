@@ -380,8 +380,12 @@ class OffsetHeadExpandFeature(_OffsetBase):
             raise NotImplementedError(model)
         return val * torch.where(b[0] > 0, torch.ones_like(b[0]), -torch.ones_like(b[0]))
 
+    def get_offsets_device(self, offset_pred, det_bboxes, img_shape=(1024, 1024)):
+        """The decoded offsets [n,2] where the kernel left them (get_offsets copies these to the host)."""
+        return K.foa_fuse_decode(self._as_four(offset_pred), det_bboxes, self.offset_coder.stds, img_shape)
+
     def get_offsets(self, offset_pred, det_bboxes, scale_factor=None, rescale=False, img_shape=(1024, 1024), with_device=False):
-        return _offsets_out(K.foa_fuse_decode(self._as_four(offset_pred), det_bboxes, self.offset_coder.stds, img_shape), with_device)
+        return _offsets_out(self.get_offsets_device(offset_pred, det_bboxes, img_shape), with_device)
 
     def merge_view_offsets(self, offset_pred, view_rois, V, table, img_shape=(1024, 1024), with_device=False):
         """Test-time augmentation: the head's output for the view-major RoIs [V n,5] -> np.float32 [n,2] in the original frame --
@@ -427,11 +431,14 @@ class OffsetHead(_OffsetBase):
             return t if self.reg_num == 2 else torch.stack([t[:, 0], torch.cos(t[:, 1]), torch.sin(t[:, 1])], -1)
         return K.offset_targets(pos_bboxes, pos_gt_offsets, self.offset_coder.means, self.offset_coder.stds, self.reg_num)
 
+    def get_offsets_device(self, offset_pred, det_bboxes, img_shape=(1024, 1024)):
+        """The decoded offsets [n,2] where the kernel left them (get_offsets copies these to the host)."""
+        return K.offset_decode(offset_pred, det_bboxes, self.offset_coder.means, self.offset_coder.stds, img_shape,
+                               polar=self.offset_coordinate == 'polar')
+
     def get_offsets(self, offset_pred, det_bboxes, scale_factor=None, rescale=False, img_shape=(1024, 1024), with_device=False):
         """offset_head.py:190-243 -> np.float32 [n,2] (pixels of the network input; scale_factor is ignored there too)."""
-        o = K.offset_decode(offset_pred, det_bboxes, self.offset_coder.means, self.offset_coder.stds, img_shape,
-                            polar=self.offset_coordinate == 'polar')
-        return _offsets_out(o, with_device)
+        return _offsets_out(self.get_offsets_device(offset_pred, det_bboxes, img_shape), with_device)
 
     def merge_view_offsets(self, offset_pred, view_rois, V, table, img_shape=(1024, 1024), with_device=False):
         """Test-time augmentation: see OffsetHeadExpandFeature.merge_view_offsets; offset_decode per view."""
@@ -766,6 +773,42 @@ class LoftRoIHead(nn.Module):
             self.last_device_masks = pasted if self.with_mask else None
             self.last_dets, self.last_det_labels = db, dl              # detection order = the order of the bitmaps and offsets
         return bbox_results, segm_results, offset_results
+
+    @torch.no_grad()
+    def simple_test_device(self, x, proposal_list, img_metas):
+        """simple_test's detections of one tile as device tensors, for a consumer that finishes them on the device (bonai_amd/scene.py):
+        -> (det_bboxes [n,5], det_labels [n], class-selected mask logits [n,S,S], decoded offsets [n,2]).  The same calls in the
+        same order as simple_test up to the heads' outputs; no paste, no encoding, no host copy of a result.  Tiles have scale
+        factor 1, and ``paste_min_score`` (a filter of simple_test's result stage) is refused rather than ignored."""
+        dev = x[0].device
+        cfg = self.test_cfg
+        if cfg.get('paste_min_score') is not None:
+            raise ValueError('test_cfg.rcnn.paste_min_score filters simple_test\'s results; simple_test_device returns every detection')
+        if not self.with_mask:
+            raise NotImplementedError('simple_test_device returns mask logits: the model has no mask head')
+        if isinstance(proposal_list, (list,)):
+            props = proposal_list[0]
+        else:
+            p, cnt = proposal_list
+            props = p[0, :int(cnt[0])]
+        meta = img_metas[0]
+        if (np.asarray(meta['scale_factor'], dtype=np.float32) != 1).any():
+            raise NotImplementedError('simple_test_device: scale_factor != 1; the device path takes fixed-size tiles')
+        rois = torch.cat([props.new_zeros(props.shape[0], 1), props[:, :4]], 1)
+        cls_score, bbox_pred = self.bbox_head(self.bbox_roi_extractor(x[:self.bbox_roi_extractor.num_inputs], rois))
+        scores = torch.softmax(cls_score, dim=1)
+        bp = bbox_pred.reshape(-1, 4)
+        rr = rois[:, 1:].repeat_interleave(bbox_pred.shape[1] // 4, dim=0)
+        bboxes = self.bbox_head.bbox_coder.decode(rr, bp, max_shape=meta['img_shape']).view(rois.shape[0], -1)
+        det_bboxes, det_labels = self.multiclass_nms(bboxes, scores, cfg.score_thr, cfg.nms, cfg.max_per_img)
+        if det_bboxes.shape[0] == 0:                # no head runs: the logits' S is not known, they are [0,0,0]
+            return det_bboxes, det_labels, det_bboxes.new_zeros((0, 0, 0)), det_bboxes.new_zeros((0, 2))
+        _bboxes = det_bboxes[:, :4]
+        det_rois = torch.cat([_bboxes.new_zeros(_bboxes.shape[0], 1), _bboxes], 1).contiguous()
+        mask_pred = self.mask_head(self.mask_roi_extractor(x[:self.mask_roi_extractor.num_inputs], det_rois))
+        sel = mask_pred[torch.arange(mask_pred.shape[0], device=dev), 0 if self.mask_head.class_agnostic else det_labels]
+        offsets = self.offset_head.get_offsets_device(self._offset_forward(x, det_rois), _bboxes.contiguous()).float()
+        return det_bboxes, det_labels, sel.float(), offsets
 
     @torch.no_grad()
     def aug_test(self, x, proposals, img_metas, elems, rescale=False):

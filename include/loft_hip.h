@@ -692,6 +692,29 @@ int loft_mask_paste_views(const float* logits, const float* boxes, int N, int V,
 int loft_mask_rle(const float* logits, const float* boxes, const float* offsets, int N, int V, int S, const int32_t* views, int img_h,
                   int img_w, float thr, void* runs, int64_t run_cap, uint8_t* out, int64_t byte_cap, void* meta, void* stream);
 
+/* ---- whole-scene inference: tiles of one uploaded image, detections merged on their masks (bonai_amd/csrc/scene.hip) ----------------
+ * An extension: the reference delegates the merge of tile results to an external package.
+ * loft_scene_tile_prep: scene uint8 [H,W,3] (H * W < 2^31), origins DEVICE int32 [n][2] = (x0, y0) -> out fp32 [n,3,th,tw]: tile i is
+ * the scene's pixels [y0, y0 + th) x [x0, x0 + tw) under loft_image_prep_d4's Normalize + HWC -> CHW (channels reversed unless
+ * channels_kept), and exactly 0.0f where the tile leaves the scene (Pad after Normalize).  One launch.
+ * loft_scene_pair_counts: logits fp32 [N,S,S] (class selected, S <= 64), boxes fp32 [N,4] in the SCENE frame, tile int32 [N] (the
+ * tile each detection came from), all DEVICE.  The mask of detection i is loft_mask_paste's bitmap of (logits[i], boxes[i]) on the
+ * H x W canvas, which is never built.  area int32 [N]: its pixel count.  recs int32 [rec_cap][3]: one record (i, j, |mask_i & mask_j|),
+ * i < j, per pair with tile[i] != tile[j] whose integer paste windows intersect (a count of 0 is a record too), each in a slot
+ * reserved on an atomic cursor: their order varies between launches.  meta: DEVICE int64 [2], zeroed here: [0] records needed,
+ * [1] nonzero when one did not fit -- nothing is written past rec_cap, and rec_cap = [0] suffices for a second call.
+ * hipErrorInvalidValue for N > 65536, S > 64 or H * W >= 2^31.
+ * loft_scene_suppress: recs int32 [R][3] as above, area int32 [N], rank int32 [N] (a permutation: 0 = highest priority) -> keep uint8
+ * [N], greedy suppression in rank order: a detection is dropped iff a KEPT detection of lower rank shares an edge with it; a record
+ * is an edge iff inter > merge_thr * min(area_i, area_j) in fp64, strictly, and both areas are positive.  work: DEVICE scratch of
+ * 3N + 2R int32.  One workgroup; order of the records is immaterial. */
+int loft_scene_tile_prep(const uint8_t* scene, int H, int W, const int32_t* origins, int n, int th, int tw, int channels_kept,
+                         float mean0, float mean1, float mean2, float std0, float std1, float std2, float* out, void* stream);
+int loft_scene_pair_counts(const float* logits, const float* boxes, const int32_t* tile, int N, int S, int H, int W, float thr,
+                           int32_t* area, int32_t* recs, int64_t rec_cap, void* meta, void* stream);
+int loft_scene_suppress(const int32_t* recs, int64_t R, const int32_t* area, const int32_t* rank, int N, double merge_thr,
+                        int32_t* work, uint8_t* keep, void* stream);
+
 /* ---- sparse backward of the RPN head -------------------------------------------------------------
  * The RPN losses (anchor_head.py:429-497, rpn_head.py:56-80) read the head outputs only at the sampled anchors (<= 256 per
  * image of 261 888), so its backward runs on the selected pixels: level_ptrs/H/W (HOST arrays, n_levels <= 8) describe the

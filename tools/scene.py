@@ -1,0 +1,64 @@
+#!/usr/bin/env python
+"""Whole-scene inference: images of any size, cut into overlapping tiles on the device and merged on their masks
+(bonai_amd/scene.py; an extension -- the reference's tools/bonai/bonai_test.py delegates this step to an external package).
+
+    python tools/scene.py CONFIG [CHECKPOINT] IMAGE [IMAGE ...] --out results.pkl [--tile N] [--overlap N] [--merge-thr F]
+                          [--footprints]
+
+Images are decoded with PIL as the dataset decodes its tiles.  ``--out`` pickles one result tuple per image in simple_test's
+layout for an image of the scene's size: (bbox_results, segm_results as COCO RLE, offset_results[, footprint RLE with --footprints]).
+A first positional argument after CONFIG that ends in .pth / .pt is the checkpoint; without one the weights are the seeded
+initialisation (a smoke run).
+"""
+import argparse
+import os
+import pickle
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('config')
+    ap.add_argument('paths', nargs='+', metavar='[CHECKPOINT] IMAGE', help='an optional checkpoint (.pth / .pt), then the images')
+    ap.add_argument('--out', required=True)
+    ap.add_argument('--tile', type=int, help='tile side, a multiple of 32 (default: cfg.data.test.img_scale, else 1024)')
+    ap.add_argument('--overlap', type=int, default=256, help='pixels neighbouring tiles share at least')
+    ap.add_argument('--merge-thr', type=float, default=0.5,
+                    help='two detections of different tiles are one building when their masks share more than this part of the smaller')
+    ap.add_argument('--footprints', action='store_true', help='results become 4-tuples: the footprints\' RLE dicts as well')
+    args = ap.parse_args()
+    ckpt = args.paths[0] if args.paths[0].endswith(('.pth', '.pt')) else None
+    images = args.paths[1:] if ckpt else args.paths
+    if not images:
+        ap.error('no image given')
+    from bonai_amd.config import Config
+    from bonai_amd.loft import build_detector
+    from bonai_amd.scene import SceneDetector, read_image
+    cfg = Config.fromfile(args.config)
+    torch.manual_seed(0)
+    if cfg.get('fp16'):
+        from bonai_amd import lib as L
+        L.set_act16(torch.float16)
+    model = build_detector(cfg.model, train_cfg=None, test_cfg=cfg.test_cfg)
+    if ckpt:
+        from bonai_amd.checkpoint import load_checkpoint
+        load_checkpoint(model, ckpt, strict=True)
+    model = model.cuda().eval()
+    det = SceneDetector(model, tile=args.tile, overlap=args.overlap, merge_thr=args.merge_thr, footprints=args.footprints, cfg=cfg)
+    results = []
+    for path in images:
+        t0 = time.time()
+        res = det.run(read_image(path))
+        torch.cuda.synchronize()
+        print(f'{path}: {res.size[1]}x{res.size[0]}, {len(res.origins)} tiles, {len(res)} buildings, {time.time() - t0:.2f} s', flush=True)
+        results.append(res.as_result_tuple())
+    with open(args.out, 'wb') as f:
+        pickle.dump(results, f)
+
+
+if __name__ == '__main__':
+    main()
