@@ -52,7 +52,7 @@ struct RoiGeom {
     float count;
 };
 
-__device__ __forceinline__ int roi_level(const float* roi, int num_levels, int finest_scale) {
+__host__ __device__ __forceinline__ int roi_level(const float* roi, int num_levels, int finest_scale) {
     // single_level_roi_extractor.py:47-50
     float scale = sqrtf((roi[3] - roi[1]) * (roi[4] - roi[2]));
     float lv = floorf(log2f(scale / (float)finest_scale + 1e-6f));
@@ -60,7 +60,7 @@ __device__ __forceinline__ int roi_level(const float* roi, int num_levels, int f
     return (int)lv;
 }
 
-__device__ __forceinline__ RoiGeom roi_geom(const float* roi, const RoiLevels& L, int P) {
+__host__ __device__ __forceinline__ RoiGeom roi_geom(const float* roi, const RoiLevels& L, int P) {
     RoiGeom g;
     g.batch = (int)roi[0];
     g.level = L.num_levels > 1 ? roi_level(roi, L.num_levels, L.finest_scale) : 0;
@@ -76,6 +76,49 @@ __device__ __forceinline__ RoiGeom roi_geom(const float* roi, const RoiLevels& L
     int c = g.grid_h * g.grid_w;
     g.count = (float)(c > 1 ? c : 1);
     return g;
+}
+
+// ---- which form a RoI takes in the separable forward kernels: ONE place decides, for the kernels and for the host query
+// loft_roi_fwd_form alike (tests assert through it that a built RoI reaches the form it was built for) ----
+#define RF_MAX 64
+#define RF_MAXP 14
+struct RoiFoot { int x0, x1, y0, y1, Fh, Fw; };
+
+// footprint: every pixel a sample can touch (same bounds as roi_prep_kernel)
+__host__ __device__ __forceinline__ RoiFoot roi_footprint(const RoiGeom& g, int H, int W, int P) {
+    RoiFoot f;
+    const float end_w = g.start_w + g.bin_w * (float)P, end_h = g.start_h + g.bin_h * (float)P;
+    f.x0 = (int)floorf(fminf(fmaxf(fminf(g.start_w, end_w) - 1.f, 0.f), (float)(W - 1)));
+    f.x1 = (int)ceilf(fminf(fmaxf(fmaxf(g.start_w, end_w) + 1.f, 0.f), (float)(W - 1)));
+    f.y0 = (int)floorf(fminf(fmaxf(fminf(g.start_h, end_h) - 1.f, 0.f), (float)(H - 1)));
+    f.y1 = (int)ceilf(fminf(fmaxf(fmaxf(g.start_h, end_h) + 1.f, 0.f), (float)(H - 1)));
+    f.Fh = f.y1 - f.y0 + 1; f.Fw = f.x1 - f.x0 + 1;
+    return f;
+}
+
+// 8-byte separable kernel: the walk, or (sub-pixel bins, footprints / P beyond the tables) the sample loop
+__host__ __device__ __forceinline__ bool roi_sep4_walks(const RoiGeom& g, const RoiFoot& f, int P) {
+    return !(!(g.bin_h >= 1.f && g.bin_w >= 1.f) || f.Fh > RF_MAX || f.Fw > RF_MAX || P > RF_MAXP);
+}
+
+// 16-byte separable kernel: cbch != 0 -> LDS form with that channel block; else stream_ok -> separable walk; else sample loop
+struct RoiSep8Form { int cbch; bool stream_ok; };
+__host__ __device__ __forceinline__ RoiSep8Form roi_sep8_form(const RoiGeom& g, const RoiFoot& f, int C, int P, int stage_bytes,
+                                                              int min_cb, int gmax) {
+    const int Fh = f.Fh, Fw = f.Fw;
+    const bool tables_ok = Fh <= RF_MAX && Fw <= RF_MAX && P <= RF_MAXP;
+    // LDS form: channels per pass = the largest of C, C/2, C/4, .. (>= min_cb, 8 .. 64 lanes per pixel) whose footprint fits
+    int cbch = 0;
+    if (tables_ok && !(C & (C - 1)) && C >= 64 && C <= 512)
+        for (int c = C; c >= min_cb && c >= 64; c >>= 1) {
+            const int ppi = 512 / c;                                          // pixels per 1 KiB wave access
+            if ((Fh * Fw + ppi - 1) / ppi * 1024 <= stage_bytes) { cbch = c; break; }
+        }
+    const bool stream_ok = tables_ok && g.bin_h >= 1.f && g.bin_w >= 1.f;
+    // (bins of a pixel or more with many samples each: the separable walk reads every window pixel once per bin row, the LDS
+    //  form once per sample corner)
+    if (stream_ok && g.grid_h * g.grid_w > gmax) cbch = 0;
+    return RoiSep8Form{cbch, stream_ok};
 }
 
 // FOA rotation k of bin (py,px) on a PxP map: position of in[py][px] inside rot90(in, k).
@@ -153,8 +196,6 @@ __global__ __launch_bounds__(256) void roi_align_fwd_kernel(RoiLevels L, const f
 // bins or footprints beyond RF_MAX pixels take the sample loop.  Same clamping / validity rules; the fp32 sum order
 // differs from the oracle's, so this form serves bf16 only (parity tolerance 8e-3 of the map's range).
 __device__ __forceinline__ float axis_weight(float start, float bin, int grid, int p, int pix, int size);
-#define RF_MAX 64
-#define RF_MAXP 14
 
 __device__ __forceinline__ void roi_sample_bins(const RoiGeom& g, const bf16_t* fb, int H, int W, int C, int P, int n_rot, int K,
                                                 int k, bf16_t* out, int part = 0, int nsplit = 1) {
@@ -197,14 +238,9 @@ __global__ __launch_bounds__(256) void roi_align_fwd_sep_kernel(RoiLevels L, con
     const RoiGeom g = roi_geom(roi, L, P);
     const int H = L.H[g.level], W = L.W[g.level];
     const bf16_t* fb = reinterpret_cast<const bf16_t*>(L.feat[g.level]) + (size_t)g.batch * H * W * C;
-    // footprint: every pixel a sample can touch (same bounds as roi_prep_kernel)
-    const float end_w = g.start_w + g.bin_w * (float)P, end_h = g.start_h + g.bin_h * (float)P;
-    const int x0 = (int)floorf(fminf(fmaxf(fminf(g.start_w, end_w) - 1.f, 0.f), (float)(W - 1)));
-    const int x1 = (int)ceilf(fminf(fmaxf(fmaxf(g.start_w, end_w) + 1.f, 0.f), (float)(W - 1)));
-    const int y0 = (int)floorf(fminf(fmaxf(fminf(g.start_h, end_h) - 1.f, 0.f), (float)(H - 1)));
-    const int y1 = (int)ceilf(fminf(fmaxf(fmaxf(g.start_h, end_h) + 1.f, 0.f), (float)(H - 1)));
-    const int Fh = y1 - y0 + 1, Fw = x1 - x0 + 1;
-    if (!(g.bin_h >= 1.f && g.bin_w >= 1.f) || Fh > RF_MAX || Fw > RF_MAX || P > RF_MAXP) {   // block-uniform
+    const RoiFoot foot = roi_footprint(g, H, W, P);
+    const int x0 = foot.x0, y0 = foot.y0, Fh = foot.Fh, Fw = foot.Fw;
+    if (!roi_sep4_walks(g, foot, P)) {                                        // block-uniform
         roi_sample_bins(g, fb, H, W, C, P, n_rot, K, k, out);
         return;
     }
@@ -377,25 +413,12 @@ __global__ __launch_bounds__(256) void roi_align_fwd_sep8_kernel(RoiLevels L, co
     const RoiGeom g = roi_geom(roi, L, P);
     const int H = L.H[g.level], W = L.W[g.level];
     const bf16_t* fb = reinterpret_cast<const bf16_t*>(L.feat[g.level]) + (size_t)g.batch * H * W * C;
-    const float end_w = g.start_w + g.bin_w * (float)P, end_h = g.start_h + g.bin_h * (float)P;
-    const int x0 = (int)floorf(fminf(fmaxf(fminf(g.start_w, end_w) - 1.f, 0.f), (float)(W - 1)));
-    const int x1 = (int)ceilf(fminf(fmaxf(fmaxf(g.start_w, end_w) + 1.f, 0.f), (float)(W - 1)));
-    const int y0 = (int)floorf(fminf(fmaxf(fminf(g.start_h, end_h) - 1.f, 0.f), (float)(H - 1)));
-    const int y1 = (int)ceilf(fminf(fmaxf(fmaxf(g.start_h, end_h) + 1.f, 0.f), (float)(H - 1)));
-    const int Fh = y1 - y0 + 1, Fw = x1 - x0 + 1;
+    const RoiFoot foot = roi_footprint(g, H, W, P);
+    const int x0 = foot.x0, y0 = foot.y0, Fh = foot.Fh, Fw = foot.Fw;
     if (Fh > -100) RF8_STAMP(1);
-    const bool tables_ok = Fh <= RF_MAX && Fw <= RF_MAX && P <= RF_MAXP;
-    // LDS form: channels per pass = the largest of C, C/2, C/4, .. (>= min_cb, 8 .. 64 lanes per pixel) whose footprint fits
-    int cbch = 0;
-    if (tables_ok && !(C & (C - 1)) && C >= 64 && C <= 512)
-        for (int c = C; c >= min_cb && c >= 64; c >>= 1) {
-            const int ppi = 512 / c;                                          // pixels per 1 KiB wave access
-            if ((Fh * Fw + ppi - 1) / ppi * 1024 <= stage_bytes) { cbch = c; break; }
-        }
-    const bool stream_ok = tables_ok && g.bin_h >= 1.f && g.bin_w >= 1.f;
-    // (bins of a pixel or more with many samples each: the separable walk reads every window pixel once per bin row, the LDS
-    //  form below once per sample corner)
-    if (stream_ok && g.grid_h * g.grid_w > gmax) cbch = 0;
+    const RoiSep8Form form = roi_sep8_form(g, foot, C, P, stage_bytes, min_cb, gmax);      // LDS form | separable walk | sample loop
+    const int cbch = form.cbch;
+    const bool stream_ok = form.stream_ok;
     RF8_NOTE(5, (cbch ? cbch : stream_ok ? 1 : 0) | (Fh << 16) | (Fw << 24));
 #if RF8_TRACE
     if (threadIdx.x == 0) { unsigned hw; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw)); unsigned xcc; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc)); RF8_NOTE(6, hw | ((unsigned long long)xcc << 32)); }
@@ -1462,6 +1485,62 @@ LOFT_EXPORT int loft_roi_order(const int* H, const float* scales, int num_levels
     return 0;
 }
 
+// The forward kernel a launch takes and the tuning of the 16-byte separable kernel, from `variant` (bits 0-7: LOFT_ROI_AUTO |
+// _FWD_SAMPLE | _FWD_SEP4; bits 8-24: tuning, with LOFT_ROI_AUTO only).  Shared by the launch and by loft_roi_fwd_form.
+struct RoiFwdPlan { int kernel, stage_bytes, min_cb, gmax, nsplit; };
+static int roi_fwd_plan(int C, int dtype, int K, int variant, RoiFwdPlan* p) {
+    const int kern = variant & 0xff;                 // bits 8-24: tuning of the 16-byte separable kernel
+    if ((kern != LOFT_ROI_AUTO && kern != LOFT_ROI_FWD_SAMPLE && kern != LOFT_ROI_FWD_SEP4) || (variant & ~0x1ffffff) ||
+        (kern != LOFT_ROI_AUTO && (variant >> 8)))
+        return (int)hipErrorInvalidValue;
+    const bool sample_form = kern == LOFT_ROI_FWD_SAMPLE;         // the sample-order kernel also for the 16-bit type (tests, A/B)
+    // Tuning bits of `variant` (tools/probes/roi_fwd_time.py; 0 everywhere = the shipped choice):
+    //   8-15  stage size of the LDS form in KiB (shipped 24: 632 us per step for the three lists of a bench step against 664
+    //         at 40 and 672 with none; 255 = none -- every RoI streams or samples)
+    //   16-17 smallest channel block of the LDS form = 64 << bits
+    //   18-21 most samples per bin for which a RoI whose bins are a pixel or more still takes the LDS form (shipped 4)
+    //   22-24 workgroups per RoI (shipped: 2 for lists of up to 4096 RoIs -- eight workgroups per CU of very uneven length
+    //         leave the CUs 1.8 deep of 3-4 possible; 1 beyond: the duplicated set-up costs more than the tail there)
+    const int kb = (variant >> 8) & 0xff, gm = (variant >> 18) & 15, sp = (variant >> 22) & 7;
+    p->stage_bytes = kb == 255 ? 0 : (kb ? kb : 24) * 1024;
+    p->min_cb = 64 << ((variant >> 16) & 3);
+    p->gmax = gm ? gm : 4;
+    p->nsplit = 1;
+    if (dtype == LOFT_ACT16 && !sample_form && !(C & 7) && kern != LOFT_ROI_FWD_SEP4) {
+        p->kernel = LOFT_ROI_KERNEL_SEP8;
+        p->nsplit = sp ? sp : (K <= 4096 ? 2 : 1);
+    } else if (dtype == LOFT_ACT16 && !sample_form) p->kernel = LOFT_ROI_KERNEL_SEP4;
+    else if (dtype == LOFT_ACT16) p->kernel = LOFT_ROI_KERNEL_SAMPLE_16;
+    else if (dtype == LOFT_F32) p->kernel = LOFT_ROI_KERNEL_SAMPLE_F32;
+    else return (int)hipErrorInvalidValue;
+    return 0;
+}
+
+// Host only: which kernel loft_roi_align_fwd_ord launches for a list of K RoIs of these operands and which form ONE RoI of it
+// takes inside that kernel.  No device call.  (The level rule's log2f may differ by an ulp between host and device: a RoI whose
+// sqrt(w h) / finest_scale sits on a power of two can resolve to another level there.)
+LOFT_EXPORT int loft_roi_fwd_form(const int* H, const int* W, const float* scales, int num_levels, int finest_scale, int C,
+                                  int dtype, const float* roi, int K, int P, int variant, int* out) {
+    if (dtype != LOFT_F32 && dtype != LOFT_ACT16) return (int)hipErrorInvalidValue;
+    if (K <= 0 || !roi || !out || P < 1) return (int)hipErrorInvalidValue;
+    if (num_levels < 1 || num_levels > 4 || (C & 3)) return (int)hipErrorInvalidValue;
+    RoiFwdPlan plan;
+    if (roi_fwd_plan(C, dtype, K, variant, &plan)) return (int)hipErrorInvalidValue;
+    const RoiLevels L = make_levels(nullptr, H, W, scales, num_levels, finest_scale);
+    const RoiGeom g = roi_geom(roi, L, P);
+    const RoiFoot f = roi_footprint(g, L.H[g.level], L.W[g.level], P);
+    int form = LOFT_ROI_FORM_LOOP, cbch = 0;
+    if (plan.kernel == LOFT_ROI_KERNEL_SEP8) {
+        const RoiSep8Form s = roi_sep8_form(g, f, C, P, plan.stage_bytes, plan.min_cb, plan.gmax);
+        cbch = s.cbch;
+        form = s.cbch ? LOFT_ROI_FORM_LDS : (s.stream_ok ? LOFT_ROI_FORM_WALK : LOFT_ROI_FORM_LOOP);
+    } else if (plan.kernel == LOFT_ROI_KERNEL_SEP4) {
+        form = roi_sep4_walks(g, f, P) ? LOFT_ROI_FORM_WALK : LOFT_ROI_FORM_LOOP;
+    }
+    out[0] = plan.kernel; out[1] = form; out[2] = cbch; out[3] = f.Fh; out[4] = f.Fw; out[5] = plan.nsplit;
+    return 0;
+}
+
 LOFT_EXPORT int loft_roi_align_fwd_ord(const void* const* feats, const int* H, const int* W, const float* scales,
                                        int num_levels, int finest_scale, int C, int dtype, const float* rois, int K,
                                        int P, int n_rot, void* out, int variant, const int32_t* order, void* stream) {
@@ -1470,34 +1549,21 @@ LOFT_EXPORT int loft_roi_align_fwd_ord(const void* const* feats, const int* H, c
     if (num_levels < 1 || num_levels > 4 || (C & 3) || (n_rot != 1 && n_rot != 4)) return (int)hipErrorInvalidValue;
     RoiLevels L = make_levels(feats, H, W, scales, num_levels, finest_scale);
     hipStream_t s = (hipStream_t)stream;
-    const int kern = variant & 0xff;                 // bits 8-17: tuning of the 16-byte separable kernel (below)
-    if ((kern != LOFT_ROI_AUTO && kern != LOFT_ROI_FWD_SAMPLE && kern != LOFT_ROI_FWD_SEP4) || (variant & ~0x1ffffff) ||
-        (kern != LOFT_ROI_AUTO && (variant >> 8)))
-        return (int)hipErrorInvalidValue;
-    const bool sample_form = kern == LOFT_ROI_FWD_SAMPLE;         // the sample-order kernel also for the 16-bit type (tests, A/B)
+    RoiFwdPlan plan;
+    if (roi_fwd_plan(C, dtype, K, variant, &plan)) return (int)hipErrorInvalidValue;
     const dim3 grid(order ? 8 * ((K + 7) / 8) : K);
-    if (dtype == LOFT_ACT16 && !sample_form && !(C & 7) && kern != LOFT_ROI_FWD_SEP4)
-    {
-        // Tuning bits of `variant` (tools/probes/roi_fwd_time.py; 0 everywhere = the shipped choice):
-        //   8-15  stage size of the LDS form in KiB (shipped 24: 632 us per step for the three lists of a bench step against 664
-        //         at 40 and 672 with none; 255 = none -- every RoI streams or samples)
-        //   16-17 smallest channel block of the LDS form = 64 << bits
-        //   18-21 most samples per bin for which a RoI whose bins are a pixel or more still takes the LDS form (shipped 4)
-        //   22-24 workgroups per RoI (shipped: 2 for lists of up to 4096 RoIs -- eight workgroups per CU of very uneven length
-        //         leave the CUs 1.8 deep of 3-4 possible; 1 beyond: the duplicated set-up costs more than the tail there)
-        const int kb = (variant >> 8) & 0xff, stage_bytes = kb == 255 ? 0 : (kb ? kb : 24) * 1024, min_cb = 64 << ((variant >> 16) & 3);
-        const int gm = (variant >> 18) & 15, gmax = gm ? gm : 4;
-        const int sp = (variant >> 22) & 7, nsplit = sp ? sp : (K <= 4096 ? 2 : 1);
+    if (plan.kernel == LOFT_ROI_KERNEL_SEP8) {
+        const int stage_bytes = plan.stage_bytes, min_cb = plan.min_cb, gmax = plan.gmax, nsplit = plan.nsplit;
         if (stage_bytes > 48 * 1024)
             hipFuncSetAttribute((const void*)roi_align_fwd_sep8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
         hipLaunchKernelGGL(roi_align_fwd_sep8_kernel, dim3(grid.x * nsplit), dim3(256), stage_bytes, s, L, rois, K, C, P, n_rot, (bf16_t*)out, order,
                            stage_bytes, min_cb, gmax, nsplit);
     }
-    else if (dtype == LOFT_ACT16 && !sample_form)
+    else if (plan.kernel == LOFT_ROI_KERNEL_SEP4)
         hipLaunchKernelGGL(roi_align_fwd_sep_kernel, grid, dim3(256), 0, s, L, rois, K, C, P, n_rot, (bf16_t*)out, order);
-    else if (dtype == LOFT_ACT16)
+    else if (plan.kernel == LOFT_ROI_KERNEL_SAMPLE_16)
         hipLaunchKernelGGL(roi_align_fwd_kernel<bf16_t>, grid, dim3(256), 0, s, L, rois, K, C, P, n_rot, (bf16_t*)out, order);
-    else if (dtype == LOFT_F32)
+    else if (plan.kernel == LOFT_ROI_KERNEL_SAMPLE_F32)
         hipLaunchKernelGGL(roi_align_fwd_kernel<float>, grid, dim3(256), 0, s, L, rois, K, C, P, n_rot, (float*)out, order);
     else
         return (int)hipErrorInvalidValue;

@@ -165,13 +165,18 @@ ROI_FWD_SORT_MIN = None
 ROI_BWD_VARIANT = ROI_AUTO
 
 
-def roi_align_fwd(feats, rois, P, strides, finest_scale=56, n_rot=1):
+def roi_align_fwd(feats, rois, P, strides, finest_scale=56, n_rot=1, out=None):
+    """out: a preallocated channels_last [n_rot K, C, P, P] tensor of the features' dtype to write (tests pre-fill it)."""
     lib = L.load()
     L.dev_check(rois, *feats)
     feats = [_nhwc(f) for f in feats]
     rois = rois.float().contiguous()
     K, C = rois.shape[0], feats[0].shape[1]
-    out = empty_nhwc(n_rot * K, C, P, P, feats[0].dtype, rois.device)
+    if out is None:
+        out = empty_nhwc(n_rot * K, C, P, P, feats[0].dtype, rois.device)
+    elif (tuple(out.shape) != (n_rot * K, C, P, P) or out.dtype != feats[0].dtype or not out.is_cuda
+          or not out.is_contiguous(memory_format=torch.channels_last)):
+        raise L.LoftHipError('roi_align_fwd: `out` must be a channels_last device tensor [n_rot K, C, P, P] of the features\' dtype')
     if K == 0:
         return out
     H, W, S = _level_args(feats, strides)
@@ -190,15 +195,25 @@ def roi_align_fwd(feats, rois, P, strides, finest_scale=56, n_rot=1):
 
 
 def roi_align_bwd(grad_out, rois, feat_shapes, P, strides, finest_scale=56, n_rot=1, grad_feats=None,
-                  rois_sorted=False, out_dtype=torch.float32):
-    """Writes (or, with grad_feats supplied, accumulates into) NHWC gradient maps of out_dtype and returns them."""
+                  rois_sorted=False, out_dtype=torch.float32, out=None):
+    """Writes (or, with grad_feats supplied, accumulates into) NHWC gradient maps of out_dtype and returns them.
+    out: preallocated maps to write instead of fresh ones (tests pre-fill them)."""
     lib = L.load()
     L.dev_check(grad_out, rois)
     grad_out = _nhwc(grad_out)
     rois = rois.float().contiguous()
     K, C = rois.shape[0], grad_out.shape[1]
     accumulate = grad_feats is not None
-    if grad_feats is None:
+    if grad_feats is None and out is not None:
+        grad_feats = list(out)
+        if len(grad_feats) != len(feat_shapes) or any(
+                tuple(g.shape) != tuple(sh) or g.dtype != out_dtype or not g.is_cuda
+                or not g.is_contiguous(memory_format=torch.channels_last) for g, sh in zip(grad_feats, feat_shapes)):
+            raise L.LoftHipError('roi_align_bwd: `out` must be one channels_last device map of out_dtype per entry of feat_shapes')
+        if K == 0:
+            for g in grad_feats:
+                g.zero_()
+    elif grad_feats is None:
         mk = zeros_nhwc if K == 0 else empty_nhwc
         grad_feats = [mk(s[0], s[1], s[2], s[3], out_dtype, rois.device) for s in feat_shapes]
     if K == 0:
@@ -262,6 +277,32 @@ class _RoIAlign(torch.autograd.Function):
 def roi_align(feats, rois, P, strides, finest_scale=56, n_rot=1):
     """Differentiable multi-level RoIAlign (SingleRoIExtractor.forward in one launch)."""
     return _RoIAlign.apply(rois, P, tuple(strides), finest_scale, n_rot, *feats)
+
+
+# LOFT_ROI_KERNEL_* / LOFT_ROI_FORM_*: what roi_fwd_form answers
+ROI_KERNEL_SAMPLE_F32, ROI_KERNEL_SAMPLE_16, ROI_KERNEL_SEP4, ROI_KERNEL_SEP8 = 1, 2, 3, 4
+ROI_FORM_LDS, ROI_FORM_WALK, ROI_FORM_LOOP = 1, 2, 3
+
+
+def roi_fwd_variant(kernel=ROI_AUTO, stage_kib=0, min_cb=0, gmax=0, nsplit=0):
+    """`variant` of loft_roi_align_fwd_ord: a forced kernel, or ROI_AUTO with the tuning of the 16-byte separable kernel (0 = the
+    shipped value): LDS stage size in KiB (255: none), smallest channel block = 64 << min_cb, most samples per bin of a RoI with
+    bins of a pixel or more that still takes the LDS form, workgroups per RoI."""
+    return int(kernel) | int(stage_kib) << 8 | int(min_cb) << 16 | int(gmax) << 18 | int(nsplit) << 22
+
+
+def roi_fwd_form(feat_hw, strides, C, dtype, roi, K, P, finest_scale=56, variant=ROI_AUTO):
+    """-> (kernel, form, cbch, Fh, Fw, nsplit): the forward kernel roi_align_fwd launches for a list of K RoIs over maps of
+    feat_hw = [(H, W), ...] with C channels of `dtype` (ROI_KERNEL_*), and the form `roi` (five floats) takes inside it
+    (ROI_FORM_*; cbch: channel block of the LDS form; Fh x Fw: footprint; nsplit: workgroups per RoI).  Asks the launch path's own
+    decision (loft_roi_fwd_form); touches no device.  Raises for arguments the launch rejects."""
+    lib = L.load()
+    out = L.arr(c_int, [0] * 6)
+    L.check(lib.loft_roi_fwd_form(L.arr(c_int, [int(h) for h, _ in feat_hw]), L.arr(c_int, [int(w) for _, w in feat_hw]),
+                                  L.arr(c_float, [1.0 / s for s in strides]), len(feat_hw), int(finest_scale), int(C), L._DT[dtype],
+                                  L.arr(c_float, [float(v) for v in roi]), int(K), int(P), int(variant), out),
+            'loft_roi_fwd_form')
+    return tuple(out)
 
 
 def map_roi_levels(rois, num_levels=4, finest_scale=56):

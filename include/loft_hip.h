@@ -79,6 +79,22 @@ int loft_roi_order(const int* H_host, const float* scales_host, int num_levels, 
 int loft_roi_align_fwd_ord(const void* const* feats_host, const int* H_host, const int* W_host, const float* scales_host,
                            int num_levels, int finest_scale, int C, int dtype, const float* rois, int K, int P,
                            int n_rot, void* out, int variant, const int32_t* order, void* stream);
+/* Which forward kernel loft_roi_align_fwd_ord launches for a list of K RoIs of these operands, and which form ONE RoI of the list
+ * (roi_host: its five floats, HOST memory) takes inside it -- the separable kernels choose per RoI.  The launch path's own
+ * decision functions, host only: no device is touched (tests).  `variant` as for loft_roi_align_fwd_ord: the same tuning bits,
+ * the same refusals.  out_host[6] = kernel (LOFT_ROI_KERNEL_*), form (LOFT_ROI_FORM_*), channel block of the LDS form (else 0),
+ * footprint rows Fh, footprint columns Fw, workgroups per RoI.  -> 0, or hipErrorInvalidValue for what the launch rejects (and
+ * for K < 1).  The level rule uses log2f: a RoI whose sqrt(w h) / finest_scale lies within an ulp of a power of two may resolve to
+ * another level on the device. */
+#define LOFT_ROI_KERNEL_SAMPLE_F32 1   /* roi_align_fwd_kernel<float> */
+#define LOFT_ROI_KERNEL_SAMPLE_16 2    /* roi_align_fwd_kernel<16-bit> */
+#define LOFT_ROI_KERNEL_SEP4 3         /* the separable kernel with 8-byte accesses */
+#define LOFT_ROI_KERNEL_SEP8 4         /* the separable kernel with 16-byte accesses (shipped) */
+#define LOFT_ROI_FORM_LDS 1            /* footprint staged in LDS, bins in sample order (16-byte kernel only) */
+#define LOFT_ROI_FORM_WALK 2           /* the separable walk */
+#define LOFT_ROI_FORM_LOOP 3           /* the sample loop (the only form of the sample-order kernels) */
+int loft_roi_fwd_form(const int* H_host, const int* W_host, const float* scales_host, int num_levels, int finest_scale, int C,
+                      int dtype, const float* roi_host, int K, int P, int variant, int* out_host);
 int loft_roi_align_bwd_v(void* const* grad_feats_host, const int* H_host, const int* W_host, const float* scales_host,
                          int num_levels, int finest_scale, int C, int dtype, const float* rois, int K, int P,
                          int n_rot, const void* grad_out, int B, int accumulate, int rois_sorted, void* workspace,
