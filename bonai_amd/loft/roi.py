@@ -17,6 +17,7 @@ import torch
 from torch import nn
 
 from .. import kernels as K
+from .. import rle
 from ..debug import DBG
 from .. import nn as F2
 from .backbone import ConvW
@@ -246,6 +247,23 @@ class _OffsetBase(nn.Module):
             return dict(loss_offset=offset_pred.sum() * 0)
         return dict(loss_offset=self.loss_offset(offset_pred, offset_targets))
 
+    foa = False          # OffsetHeadExpandFeature: offset_pred holds the rotation branches, fused by the decode kernels
+
+    def _as_four(self, offset_pred):
+        return offset_pred
+
+    def get_offsets(self, offset_pred, det_bboxes, scale_factor=None, rescale=False, img_shape=(1024, 1024), with_device=False):
+        """offset_head.py:190-243 / offset_head_expand_feature.py:415-448 -> np.float32 [n,2] (pixels of the network input;
+        scale_factor is ignored there too); the subclass's get_offsets_device, copied to the host."""
+        return _offsets_out(self.get_offsets_device(offset_pred, det_bboxes, img_shape), with_device)
+
+    def merge_view_offsets(self, offset_pred, view_rois, V, table, img_shape=(1024, 1024), with_device=False):
+        """Test-time augmentation: the head's output for the view-major RoIs [V n,5] -> np.float32 [n,2] in the original frame --
+        get_offsets per view, the vector mapped back, mean over the views, one launch."""
+        return _offsets_out(K.tta_merge_offsets(self._as_four(offset_pred), view_rois, V, table, self.offset_coder.means,
+                                                self.offset_coder.stds, img_shape, foa=self.foa,
+                                                polar=self.offset_coordinate == 'polar'), with_device)
+
 
 class _BranchSlabs(torch.autograd.Function):
     """[E N,C,H,W] branch-major NHWC batch -> its E [N,C,H,W] slabs (views); the backward concatenates the slab
@@ -289,6 +307,7 @@ class OffsetHeadExpandFeature(_OffsetBase):
     """FOA: rotated copies of the RoI feature (4 in configs/loft_foa; 2 or 3 in the reference's other rotation sets), per-branch
     num_convs x (conv3x3+ReLU), then the FC stack + regressor -- shared by the branches (``share_expand_fc=True``,
     configs/loft_foa) or one per branch (the reference class's default)."""
+    foa = True
 
     def __init__(self, roi_feat_size=7, in_channels=256, num_convs=4, num_fcs=2, reg_num=2, conv_out_channels=256,
                  fc_out_channels=1024, expand_feature_num=4, share_expand_fc=False, rotations=[0, 90, 180, 270],
@@ -384,15 +403,6 @@ class OffsetHeadExpandFeature(_OffsetBase):
         """The decoded offsets [n,2] where the kernel left them (get_offsets copies these to the host)."""
         return K.foa_fuse_decode(self._as_four(offset_pred), det_bboxes, self.offset_coder.stds, img_shape)
 
-    def get_offsets(self, offset_pred, det_bboxes, scale_factor=None, rescale=False, img_shape=(1024, 1024), with_device=False):
-        return _offsets_out(self.get_offsets_device(offset_pred, det_bboxes, img_shape), with_device)
-
-    def merge_view_offsets(self, offset_pred, view_rois, V, table, img_shape=(1024, 1024), with_device=False):
-        """Test-time augmentation: the head's output for the view-major RoIs [V n,5] -> np.float32 [n,2] in the original frame --
-        get_offsets per view, the vector mapped back, mean over the views, one launch."""
-        return _offsets_out(K.tta_merge_offsets(self._as_four(offset_pred), view_rois, V, table, stds=self.offset_coder.stds,
-                                                max_shape=img_shape, foa=True), with_device)
-
 
 @HEADS.register_module()
 class OffsetHead(_OffsetBase):
@@ -436,15 +446,6 @@ class OffsetHead(_OffsetBase):
         return K.offset_decode(offset_pred, det_bboxes, self.offset_coder.means, self.offset_coder.stds, img_shape,
                                polar=self.offset_coordinate == 'polar')
 
-    def get_offsets(self, offset_pred, det_bboxes, scale_factor=None, rescale=False, img_shape=(1024, 1024), with_device=False):
-        """offset_head.py:190-243 -> np.float32 [n,2] (pixels of the network input; scale_factor is ignored there too)."""
-        return _offsets_out(self.get_offsets_device(offset_pred, det_bboxes, img_shape), with_device)
-
-    def merge_view_offsets(self, offset_pred, view_rois, V, table, img_shape=(1024, 1024), with_device=False):
-        """Test-time augmentation: see OffsetHeadExpandFeature.merge_view_offsets; offset_decode per view."""
-        return _offsets_out(K.tta_merge_offsets(offset_pred, view_rois, V, table, self.offset_coder.means, self.offset_coder.stds,
-                                                img_shape, foa=False, polar=self.offset_coordinate == 'polar'), with_device)
-
 
 def _offsets_out(o, with_device):
     """Decoded offsets [n,2] on the device -> np.float32 [n,2]; ``with_device``: (that, the fp32 device tensor it was copied from) --
@@ -465,6 +466,41 @@ def _result_mode(cfg):
     if footprints and not fused:
         raise ValueError("test_cfg.rcnn: footprint_rle=True needs rle_masks='fused'")
     return fused, footprints
+
+
+def _unpack_proposals(proposal_list):
+    """The first image's proposals [n,>=4]: from RPNHead's (proposals [B,P,5], counts [B]) or the reference's list of tensors."""
+    if isinstance(proposal_list, (list,)):
+        return proposal_list[0]
+    p, cnt = proposal_list
+    return p[0, :int(cnt[0])]
+
+
+def _view_rois(boxes, views, img_shape):
+    """boxes [n,>=4] of one image -> its RoIs [n,5] (bbox2roi); with views = (V, table) the RoIs [V n,5], view-major, of the boxes
+    mapped into each view of shape ``img_shape``: the RoIs of view v carry batch index v."""
+    if views is None:
+        return torch.cat([boxes.new_zeros(boxes.shape[0], 1), boxes[:, :4]], 1)
+    return K.tta_view_rois(boxes, views[1], views[0], img_shape[0], img_shape[1])
+
+
+def results_by_class(items, labels, num_classes):
+    """Per-detection results in detection order -> the reference's per-class layout (bbox2result, test_mixins.py:171-176): an
+    array [n,...] becomes ``num_classes`` arrays, a list ``num_classes`` lists; the detection order is kept inside a class."""
+    if isinstance(items, np.ndarray):
+        return [items[labels == c] for c in range(num_classes)]
+    out = [[] for _ in range(num_classes)]
+    for r, l in zip(items, labels):
+        out[int(l)].append(r)
+    return out
+
+
+def empty_results(num_classes, with_mask=True, footprints=False):
+    """The result tuple of an image without detections: (bbox_results, segm_results, offset_results[, footprint_results])."""
+    def per_class():
+        return [[] for _ in range(num_classes)] if with_mask else None
+    out = ([np.zeros((0, 5), dtype=np.float32) for _ in range(num_classes)], per_class(), [[] for _ in range(2)])
+    return out + (per_class(),) if footprints else out
 
 
 def _masks_to_device(gt_masks, device):
@@ -688,31 +724,29 @@ class LoftRoIHead(nn.Module):
             dets, keep = dets[:max_num], keep[:max_num]
         return dets, labels[keep]
 
-    @torch.no_grad()
-    def simple_test(self, x, proposal_list, img_metas, proposals=None, rescale=False):
-        """loft_roi_head.py:196-227 (+ test_mixins.py:53-72,152-177,213-241): one image ->
-        (bbox_results, segm_results, offset_results) with the reference's types; with test_cfg.rcnn.footprint_rle a fourth
-        element, the footprints' RLE dicts in segm_results' layout."""
-        fused, footprints = _result_mode(self.test_cfg)
-        dev = x[0].device
-        if isinstance(proposal_list, (list,)):
-            props = proposal_list[0]
-        else:
-            p, cnt = proposal_list
-            props = p[0, :int(cnt[0])]
-        meta = img_metas[0]
-        img_shape, scale_factor, ori_shape = meta['img_shape'], meta['scale_factor'], meta['ori_shape']
-        rois = torch.cat([props.new_zeros(props.shape[0], 1), props[:, :4]], 1)
-        cfg = self.test_cfg
+    # simple_test, aug_test and simple_test_device are one detection stage (_detect) and, for the two that return the host tuple, one
+    # result stage (_results).  What differs between one image and the V views of one is carried by ``views``: None, or
+    # (V, the device table of kernels.tta_view_table).
+
+    def _detect(self, x, boxes, meta, views=None, scale_factor=None):
+        """Detection stage: proposals [n,>=4] -> bbox head -> merged boxes and scores -> multiclass_nms -> the opt-in
+        ``paste_min_score`` filter -> (det_bboxes [k,5], det_labels [k], sf).  One image: softmax + decode (test_mixins.py:53-72);
+        ``scale_factor`` (simple_test's rescale) divides the boxes, and sf is that factor on the device, else None.  Views: every
+        head runs once over all of them and kernels.tta_merge_bboxes is aug_test_bboxes' per-view softmax / decode / map back / mean."""
+        cfg, img_shape = self.test_cfg, meta['img_shape']
+        rois = _view_rois(boxes, views, img_shape)
         cls_score, bbox_pred = self.bbox_head(self.bbox_roi_extractor(x[:self.bbox_roi_extractor.num_inputs], rois))
-        scores = torch.softmax(cls_score, dim=1)
-        ncls = self.bbox_head.num_classes
-        bp = bbox_pred.reshape(-1, 4)
-        rr = rois[:, 1:].repeat_interleave(bbox_pred.shape[1] // 4, dim=0)
-        bboxes = self.bbox_head.bbox_coder.decode(rr, bp, max_shape=img_shape).view(rois.shape[0], -1)
-        sf = torch.as_tensor(np.asarray(scale_factor, dtype=np.float32), device=dev)
-        if rescale:
-            bboxes = (bboxes.view(bboxes.size(0), -1, 4) / sf).view(bboxes.size(0), -1)
+        coder, sf = self.bbox_head.bbox_coder, None
+        if views is None:
+            scores = torch.softmax(cls_score, dim=1)
+            rr = rois[:, 1:].repeat_interleave(bbox_pred.shape[1] // 4, dim=0)
+            bboxes = coder.decode(rr, bbox_pred.reshape(-1, 4), max_shape=img_shape).view(rois.shape[0], -1)
+            if scale_factor is not None:
+                sf = torch.as_tensor(np.asarray(scale_factor, dtype=np.float32), device=bboxes.device)
+                bboxes = (bboxes.view(bboxes.size(0), -1, 4) / sf).view(bboxes.size(0), -1)
+        else:
+            bboxes, scores = K.tta_merge_bboxes(rois, bbox_pred, cls_score, views[0], views[1], img_shape[0], img_shape[1],
+                                                coder.means, coder.stds)
         det_bboxes, det_labels = self.multiclass_nms(bboxes, scores, cfg.score_thr, cfg.nms, cfg.max_per_img)
         if cfg.get('paste_min_score') is not None and det_bboxes.shape[0]:
             # opt-in (bonai_amd/validate.py sets it to the metric's score threshold): detections whose FINAL score is below it are
@@ -720,172 +754,132 @@ class LoftRoIHead(nn.Module):
             # spend anything on them.  Absent: every detection above test_cfg.rcnn.score_thr goes on, as the result pickle needs.
             strong = det_bboxes[:, 4] >= float(cfg['paste_min_score'])
             det_bboxes, det_labels = det_bboxes[strong], det_labels[strong]
-        db = det_bboxes.cpu().numpy()
+        return det_bboxes, det_labels, sf
+
+    def _mask_logits(self, x, det_rois, det_labels, views=None):
+        """Mask head over the detections' RoIs -> the logits of each detection's class, [n,S,S]; with views [V,n,S,S]."""
+        mask_pred = self.mask_head(self.mask_roi_extractor(x[:self.mask_roi_extractor.num_inputs], det_rois))
+        if self.mask_head.class_agnostic:
+            cls_idx = 0
+        else:
+            cls_idx = det_labels if views is None else det_labels.repeat(views[0])
+        sel = mask_pred[torch.arange(mask_pred.shape[0], device=mask_pred.device), cls_idx]
+        return sel if views is None else sel.reshape(views[0], -1, sel.shape[-2], sel.shape[-1])
+
+    def _results(self, x, det_bboxes, det_labels, meta, mode, views=None, sf=None):
+        """Result stage: _detect's detections -> (bbox_results, segm_results, offset_results) with the reference's types
+        (test_mixins.py:152-177,213-241; the views' masks as aug_test_mask, test_mixins.py:179-208, merges them) and, with
+        ``footprint_rle``, the footprints' RLE dicts in segm_results' layout as a fourth element.  mode: _result_mode's pair."""
+        fused, footprints = mode
+        cfg, ncls = self.test_cfg, self.bbox_head.num_classes
+        db = det_bboxes.cpu().numpy()                  # the host learns the detections before the mask head is enqueued
         dl = det_labels.cpu().numpy()
-        bbox_results = [db[dl == i, :] for i in range(ncls)] if db.shape[0] else \
-            [np.zeros((0, 5), dtype=np.float32) for _ in range(ncls)]
-        if det_bboxes.shape[0] == 0:
-            segm = [[] for _ in range(ncls)] if self.with_mask else None
-            empty = (bbox_results, segm, [[] for _ in range(2)])
-            return empty + ([[] for _ in range(ncls)] if self.with_mask else None,) if footprints else empty
-        _bboxes = det_bboxes[:, :4] * sf if rescale else det_bboxes[:, :4]
-        det_rois = torch.cat([_bboxes.new_zeros(_bboxes.shape[0], 1), _bboxes], 1).contiguous()
-        segm_results = None
+        if db.shape[0] == 0:
+            return empty_results(ncls, self.with_mask, footprints)
+        bbox_results = results_by_class(db, dl, ncls)
+        boxes = det_bboxes[:, :4]                      # in the network input's frame: the RoIs' and the offsets'
+        if sf is not None:
+            boxes = boxes * sf
+        if views is not None:
+            boxes = boxes.contiguous()
+        det_rois = _view_rois(boxes, views, meta['img_shape'])
+        table = None if views is None else views[1]
+        segm_results = pasted = None
         if self.with_mask:
-            mask_pred = self.mask_head(self.mask_roi_extractor(x[:self.mask_roi_extractor.num_inputs], det_rois))
-            sel = mask_pred[torch.arange(mask_pred.shape[0], device=dev), 0 if self.mask_head.class_agnostic else det_labels]
-            if rescale:
-                img_h, img_w = ori_shape[:2]
-                pb = _bboxes / sf
+            sel = self._mask_logits(x, det_rois, det_labels, views)
+            if views is None and sf is None:           # not rescaled: the canvas is ori_shape * scale_factor
+                s = np.asarray(meta['scale_factor']).reshape(-1)
+                img_h = int(np.round(meta['ori_shape'][0] * float(s[1 if s.size > 1 else 0])))
+                img_w = int(np.round(meta['ori_shape'][1] * float(s[0])))
             else:
-                img_h = int(np.round(ori_shape[0] * float(np.asarray(scale_factor).reshape(-1)[1 if np.size(scale_factor) > 1 else 0])))
-                img_w = int(np.round(ori_shape[1] * float(np.asarray(scale_factor).reshape(-1)[0])))
-                pb = _bboxes
-            pasted = None if fused else K.mask_paste(sel, pb.contiguous(), img_h, img_w, cfg.mask_thr_binary)
-            segm_results = [[] for _ in range(ncls)]
+                img_h, img_w = meta['ori_shape'][:2]
+            pb = boxes if sf is None else boxes / sf
+            thr = cfg.mask_thr_binary
             if fused:
-                # the same strings from the logits, no bitmap (csrc/mask_rle.hip)
-                for i, r in enumerate(K.mask_paste_rle(sel, pb, img_h, img_w, cfg.mask_thr_binary)):
-                    segm_results[int(dl[i])].append(r)
-            elif cfg.get('rle_masks', False):
-                # what apis/test.py:59-67 (encode_mask_results) produces from the bool arrays, without moving them to the host:
-                # run boundaries are extracted on the device (bonai_amd.rle)
-                from ..rle import rle_encode_masks
-                for i, r in enumerate(rle_encode_masks(pasted)):
-                    segm_results[int(dl[i])].append(r)
+                # the strings from the logits, no bitmap (csrc/mask_rle.hip)
+                segm = K.mask_paste_rle(sel, pb, img_h, img_w, thr, views=table)
             else:
-                im = pasted.bool().cpu().numpy()
-                for i in range(im.shape[0]):
-                    segm_results[int(dl[i])].append(im[i])
+                pasted = K.mask_paste(sel, pb.contiguous(), img_h, img_w, thr) if views is None else \
+                    K.mask_paste_views(sel, pb, table, img_h, img_w, thr)
+                if cfg.get('rle_masks', False):
+                    # what apis/test.py:59-67 (encode_mask_results) produces from the bool arrays, without moving them to the
+                    # host: run boundaries are extracted on the device (bonai_amd.rle)
+                    segm = rle.rle_encode_masks(pasted)
+                else:
+                    segm = list(pasted.bool().cpu().numpy())
+            segm_results = results_by_class(segm, dl, ncls)
         offset_pred = self._offset_forward(x, det_rois)
-        offset_results = self.offset_head.get_offsets(offset_pred, _bboxes.contiguous(), scale_factor, rescale, with_device=footprints)
+        if views is None:
+            offset_results = self.offset_head.get_offsets(offset_pred, boxes.contiguous(), meta['scale_factor'], sf is not None,
+                                                          with_device=footprints)
+        else:
+            # an extension: StandardRoIHead.aug_test (standard_roi_head.py:264-290) returns no offsets
+            offset_results = self.offset_head.merge_view_offsets(offset_pred, det_rois, views[0], table, with_device=footprints)
         if footprints:
             offset_results, dev_offsets = offset_results
             footprint_results = None
             if self.with_mask:
-                footprint_results = [[] for _ in range(ncls)]
-                for i, r in enumerate(K.mask_paste_rle(sel, pb, img_h, img_w, cfg.mask_thr_binary, offsets=dev_offsets)):
-                    footprint_results[int(dl[i])].append(r)
+                footprint_results = results_by_class(
+                    K.mask_paste_rle(sel, pb, img_h, img_w, thr, views=table, offsets=dev_offsets), dl, ncls)
             return bbox_results, segm_results, offset_results, footprint_results
         if cfg.get('keep_device_masks', False):
             # tools/test.py --eval: the pasted roof bitmaps stay on the device for bonai_amd.evaluation (footprints by
             # kernels.mask_translate, IoU pairing) -- next to, not instead of, the result tuple
-            self.last_device_masks = pasted if self.with_mask else None
+            self.last_device_masks = pasted
             self.last_dets, self.last_det_labels = db, dl              # detection order = the order of the bitmaps and offsets
         return bbox_results, segm_results, offset_results
 
     @torch.no_grad()
+    def simple_test(self, x, proposal_list, img_metas, proposals=None, rescale=False):
+        """loft_roi_head.py:196-227: one image -> (bbox_results, segm_results, offset_results), see _results."""
+        mode = _result_mode(self.test_cfg)
+        meta = img_metas[0]
+        det_bboxes, det_labels, sf = self._detect(x, _unpack_proposals(proposal_list), meta,
+                                                  scale_factor=meta['scale_factor'] if rescale else None)
+        return self._results(x, det_bboxes, det_labels, meta, mode, sf=sf)
+
+    @torch.no_grad()
     def simple_test_device(self, x, proposal_list, img_metas):
         """simple_test's detections of one tile as device tensors, for a consumer that finishes them on the device (bonai_amd/scene.py):
-        -> (det_bboxes [n,5], det_labels [n], class-selected mask logits [n,S,S], decoded offsets [n,2]).  The same calls in the
-        same order as simple_test up to the heads' outputs; no paste, no encoding, no host copy of a result.  Tiles have scale
-        factor 1, and ``paste_min_score`` (a filter of simple_test's result stage) is refused rather than ignored."""
-        dev = x[0].device
-        cfg = self.test_cfg
-        if cfg.get('paste_min_score') is not None:
+        -> (det_bboxes [n,5], det_labels [n], class-selected mask logits [n,S,S], decoded offsets [n,2]).  simple_test's detection
+        stage and heads; no paste, no encoding, no host copy of a result.  Tiles have scale factor 1, and ``paste_min_score`` (a
+        filter for simple_test's results) is refused rather than ignored."""
+        if self.test_cfg.get('paste_min_score') is not None:
             raise ValueError('test_cfg.rcnn.paste_min_score filters simple_test\'s results; simple_test_device returns every detection')
         if not self.with_mask:
             raise NotImplementedError('simple_test_device returns mask logits: the model has no mask head')
-        if isinstance(proposal_list, (list,)):
-            props = proposal_list[0]
-        else:
-            p, cnt = proposal_list
-            props = p[0, :int(cnt[0])]
+        props = _unpack_proposals(proposal_list)
         meta = img_metas[0]
         if (np.asarray(meta['scale_factor'], dtype=np.float32) != 1).any():
             raise NotImplementedError('simple_test_device: scale_factor != 1; the device path takes fixed-size tiles')
-        rois = torch.cat([props.new_zeros(props.shape[0], 1), props[:, :4]], 1)
-        cls_score, bbox_pred = self.bbox_head(self.bbox_roi_extractor(x[:self.bbox_roi_extractor.num_inputs], rois))
-        scores = torch.softmax(cls_score, dim=1)
-        bp = bbox_pred.reshape(-1, 4)
-        rr = rois[:, 1:].repeat_interleave(bbox_pred.shape[1] // 4, dim=0)
-        bboxes = self.bbox_head.bbox_coder.decode(rr, bp, max_shape=meta['img_shape']).view(rois.shape[0], -1)
-        det_bboxes, det_labels = self.multiclass_nms(bboxes, scores, cfg.score_thr, cfg.nms, cfg.max_per_img)
+        det_bboxes, det_labels, _ = self._detect(x, props, meta)
         if det_bboxes.shape[0] == 0:                # no head runs: the logits' S is not known, they are [0,0,0]
             return det_bboxes, det_labels, det_bboxes.new_zeros((0, 0, 0)), det_bboxes.new_zeros((0, 2))
-        _bboxes = det_bboxes[:, :4]
-        det_rois = torch.cat([_bboxes.new_zeros(_bboxes.shape[0], 1), _bboxes], 1).contiguous()
-        mask_pred = self.mask_head(self.mask_roi_extractor(x[:self.mask_roi_extractor.num_inputs], det_rois))
-        sel = mask_pred[torch.arange(mask_pred.shape[0], device=dev), 0 if self.mask_head.class_agnostic else det_labels]
-        offsets = self.offset_head.get_offsets_device(self._offset_forward(x, det_rois), _bboxes.contiguous()).float()
+        boxes = det_bboxes[:, :4]
+        det_rois = _view_rois(boxes, None, None)
+        sel = self._mask_logits(x, det_rois, det_labels)
+        offsets = self.offset_head.get_offsets_device(self._offset_forward(x, det_rois), boxes.contiguous()).float()
         return det_bboxes, det_labels, sel.float(), offsets
 
     @torch.no_grad()
     def aug_test(self, x, proposals, img_metas, elems, rescale=False):
         """Test-time augmentation over the V views of one tile (x: their features as a batch of V; proposals [n,5] in the original
-        frame, from RPNHead.aug_test_rpn; elems: the views' D4 elements) -> simple_test's 3-tuple.  Boxes, scores and masks follow
+        frame, from RPNHead.aug_test_rpn; elems: the views' D4 elements) -> simple_test's tuple.  Boxes, scores and masks follow
         aug_test_bboxes + multiclass_nms and aug_test_mask (test_mixins.py:74-107,179-208, merge_augs.py); the merged offsets are an
-        extension (StandardRoIHead.aug_test, standard_roi_head.py:264-290, returns none).  Every head runs ONCE over all views -- the
-        RoIs of view v carry batch index v -- and the per-view softmax / decode / map back / mean are one launch per result
-        (bonai_amd/csrc/tta.hip).  Views have scale factor 1, so ``rescale`` changes nothing."""
-        fused, footprints = _result_mode(self.test_cfg)
-        dev = x[0].device
-        cfg = self.test_cfg
-        V = len(elems)
+        extension.  Every head runs ONCE over all views -- the RoIs of view v carry batch index v -- and the per-view softmax /
+        decode / map back / mean are one launch per result (bonai_amd/csrc/tta.hip).  Views have scale factor 1, so ``rescale``
+        changes nothing."""
+        mode = _result_mode(self.test_cfg)
         meta = img_metas[0][0]
         img_h, img_w = meta['img_shape'][:2]
         K._tta_check_shape(elems, img_h, img_w)
-        table = K.tta_view_table(elems, dev)
-        ncls = self.bbox_head.num_classes
-        rois = K.tta_view_rois(proposals, table, V, img_h, img_w)
-        cls_score, bbox_pred = self.bbox_head(self.bbox_roi_extractor(x[:self.bbox_roi_extractor.num_inputs], rois))
-        coder = self.bbox_head.bbox_coder
-        bboxes, scores = K.tta_merge_bboxes(rois, bbox_pred, cls_score, V, table, img_h, img_w, coder.means, coder.stds)
-        det_bboxes, det_labels = self.multiclass_nms(bboxes, scores, cfg.score_thr, cfg.nms, cfg.max_per_img)
-        if cfg.get('paste_min_score') is not None and det_bboxes.shape[0]:
-            strong = det_bboxes[:, 4] >= float(cfg['paste_min_score'])
-            det_bboxes, det_labels = det_bboxes[strong], det_labels[strong]
-        db = det_bboxes.cpu().numpy()
-        dl = det_labels.cpu().numpy()
-        bbox_results = [db[dl == i, :] for i in range(ncls)] if db.shape[0] else \
-            [np.zeros((0, 5), dtype=np.float32) for _ in range(ncls)]
-        if det_bboxes.shape[0] == 0:
-            segm = [[] for _ in range(ncls)] if self.with_mask else None
-            empty = (bbox_results, segm, [[] for _ in range(2)])
-            return empty + ([[] for _ in range(ncls)] if self.with_mask else None,) if footprints else empty
-        nd = det_bboxes.shape[0]
-        _bboxes = det_bboxes[:, :4].contiguous()
-        det_rois = K.tta_view_rois(_bboxes, table, V, img_h, img_w)
-        segm_results, pasted = None, None
-        if self.with_mask:
-            mask_pred = self.mask_head(self.mask_roi_extractor(x[:self.mask_roi_extractor.num_inputs], det_rois))
-            cls_idx = 0 if self.mask_head.class_agnostic else det_labels.repeat(V)
-            sel = mask_pred[torch.arange(mask_pred.shape[0], device=dev), cls_idx]
-            ori_h, ori_w = meta['ori_shape'][:2]
-            sel = sel.reshape(V, nd, sel.shape[-2], sel.shape[-1])
-            if not fused:
-                pasted = K.mask_paste_views(sel, _bboxes, table, ori_h, ori_w, cfg.mask_thr_binary)
-            segm_results = [[] for _ in range(ncls)]
-            if fused:
-                for i, r in enumerate(K.mask_paste_rle(sel, _bboxes, ori_h, ori_w, cfg.mask_thr_binary, views=table)):
-                    segm_results[int(dl[i])].append(r)
-            elif cfg.get('rle_masks', False):
-                from ..rle import rle_encode_masks
-                for i, r in enumerate(rle_encode_masks(pasted)):
-                    segm_results[int(dl[i])].append(r)
-            else:
-                im = pasted.bool().cpu().numpy()
-                for i in range(im.shape[0]):
-                    segm_results[int(dl[i])].append(im[i])
-        offset_results = self.offset_head.merge_view_offsets(self._offset_forward(x, det_rois), det_rois, V, table,
-                                                             with_device=footprints)
-        if footprints:
-            offset_results, dev_offsets = offset_results
-            footprint_results = None
-            if self.with_mask:
-                footprint_results = [[] for _ in range(ncls)]
-                for i, r in enumerate(K.mask_paste_rle(sel, _bboxes, ori_h, ori_w, cfg.mask_thr_binary, views=table,
-                                                       offsets=dev_offsets)):
-                    footprint_results[int(dl[i])].append(r)
-            return bbox_results, segm_results, offset_results, footprint_results
-        if cfg.get('keep_device_masks', False):
-            self.last_device_masks = pasted
-            self.last_dets, self.last_det_labels = db, dl
-        return bbox_results, segm_results, offset_results
+        views = (len(elems), K.tta_view_table(elems, x[0].device))
+        det_bboxes, det_labels, _ = self._detect(x, proposals, meta, views)
+        return self._results(x, det_bboxes, det_labels, meta, mode, views)
 
     def forward_dummy(self, x, proposals):
         """standard_roi_head.py:54-68: (cls_score, bbox_pred, mask_pred of the first 100 RoIs)."""
-        rois = torch.cat([proposals.new_zeros(proposals.shape[0], 1), proposals[:, :4]], 1).contiguous()
+        rois = _view_rois(proposals, None, None)
         outs = tuple(self.bbox_head(self.bbox_roi_extractor(x[:self.bbox_roi_extractor.num_inputs], rois)))
         if self.with_mask:
             outs = outs + (self.mask_head(self.mask_roi_extractor(x[:self.mask_roi_extractor.num_inputs], rois[:100].contiguous())),)

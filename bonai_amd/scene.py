@@ -64,15 +64,13 @@ class SceneResult:
     def as_result_tuple(self):
         """simple_test's layout for one image of the scene's size: (bbox_results per class, segm_results per class, offsets [M,2])
         and, with footprints, their dicts per class as a fourth element."""
+        from .loft.roi import empty_results, results_by_class
         ncls = self.num_classes
         if len(self) == 0:
-            out = ([np.zeros((0, 5), dtype=np.float32) for _ in range(ncls)], [[] for _ in range(ncls)], [[] for _ in range(2)])
-            return out + ([[] for _ in range(ncls)],) if self.footprints is not None else out
-        bbox_results = [self.bboxes[self.labels == c, :] for c in range(ncls)]
-        segm = [[r for r, l in zip(self.roofs, self.labels) if l == c] for c in range(ncls)]
-        out = (bbox_results, segm, self.offsets)
+            return empty_results(ncls, footprints=self.footprints is not None)
+        out = (results_by_class(self.bboxes, self.labels, ncls), results_by_class(self.roofs, self.labels, ncls), self.offsets)
         if self.footprints is not None:
-            out = out + ([[r for r, l in zip(self.footprints, self.labels) if l == c] for c in range(ncls)],)
+            out = out + (results_by_class(self.footprints, self.labels, ncls),)
         return out
 
 
