@@ -25,6 +25,7 @@ FLAGS = {
     'boxes.hip': ['-ffp-contract=off'],
     'deform.hip': ['-ffp-contract=off'],
     'augment.hip': ['-ffp-contract=off'],      # Normalize as subtract, then divide: bit for bit the torch chain
+    'resize.hip': ['-ffp-contract=off'],       # augment.hip's Normalize statement behind an integer resampler: the same bits
     'tta.hip': ['-ffp-contract=off'],          # shares box_codec.h with boxes.hip: a row decodes to the same bits in both
     'mask_rle.hip': ['-ffp-contract=off'],     # the paste rule of box_codec.h again: the same pixels as boxes.hip / tta.hip set
     'scene.hip': ['-ffp-contract=off'],        # box_codec.h's paste rule and augment.hip's Normalize statement: the same bits

@@ -13,36 +13,8 @@
 // different banks.
 #include "loft_common.h"
 #include "image_prep.h"
+#include "d4_tile.h"
 #include "../../include/loft_hip.h"
-
-#define D4_TILE 64
-#define D4_IMG_PITCH (D4_TILE * 3 / 4 + 1)      // dwords per LDS row of the image tile: 48 of pixels + 1 of padding = 49 (odd)
-#define D4_MASK_PITCH (D4_TILE / 4 + 1)         // dwords per LDS row of the bitmap tile: 16 + 1 = 17 (odd)
-
-struct D4Tile {            // the source tile of one output tile
-    int tw, th;            // extent of the output tile (partial at the right / bottom edge)
-    int sr0, sc0;          // first source row / column
-    int sh, sw;            // source rows / columns
-};
-
-__device__ __forceinline__ D4Tile d4_tile(int elem, int H, int W, int x0, int y0) {
-    D4Tile t;
-    t.tw = min(D4_TILE, W - x0);
-    t.th = min(D4_TILE, H - y0);
-    const int mx0 = (elem & LOFT_D4_MIRROR_X) ? W - x0 - t.tw : x0;      // where the tile's x' and y' ranges start
-    const int my0 = (elem & LOFT_D4_MIRROR_Y) ? H - y0 - t.th : y0;
-    if (elem & LOFT_D4_TRANSPOSE) { t.sr0 = mx0; t.sh = t.tw; t.sc0 = my0; t.sw = t.th; }
-    else                          { t.sr0 = my0; t.sh = t.th; t.sc0 = mx0; t.sw = t.tw; }
-    return t;
-}
-
-// (row, column) inside the LDS tile of output pixel (ox, oy) of the tile
-__device__ __forceinline__ void d4_src(int elem, const D4Tile& t, int ox, int oy, int& r, int& c) {
-    const int lx = (elem & LOFT_D4_MIRROR_X) ? t.tw - 1 - ox : ox;
-    const int ly = (elem & LOFT_D4_MIRROR_Y) ? t.th - 1 - oy : oy;
-    r = (elem & LOFT_D4_TRANSPOSE) ? lx : ly;
-    c = (elem & LOFT_D4_TRANSPOSE) ? ly : lx;
-}
 
 // ---- Normalize + DefaultFormatBundle's HWC -> CHW under one element per sample -------------------------------------------------
 // img uint8 [n, H, W, 3], elems int32 [n], out fp32 [n, 3, H, W].  One lane per output pixel and channel plane: a wavefront
@@ -97,8 +69,6 @@ LOFT_EXPORT int loft_image_prep_d4(const uint8_t* img, const int32_t* elems, int
 // element makes a lane read one byte from each of FOUR consecutive LDS rows, and a stride of four rows reaches only eight banks
 // at any odd pitch; so every block of 32 rows is skewed by one more dword, and the two 16-lane halves of a bank group take output
 // rows eight apart (two dwords apart in LDS): 4 * (g % 8) + (g / 8) + {0, 2} covers the 32 banks once.
-__device__ __forceinline__ int mask_lds_row(int r) { return r * D4_MASK_PITCH + (r >> 5); }
-
 __global__ __launch_bounds__(256) void mask_d4_kernel(const uint8_t* __restrict__ in, int elem, int H, int W, uint8_t* __restrict__ out) {
     __shared__ unsigned tile[D4_TILE * D4_MASK_PITCH + 2];
     const int k = blockIdx.z, x0 = blockIdx.x * D4_TILE, y0 = blockIdx.y * D4_TILE;

@@ -129,9 +129,10 @@ def flip_sample(sample, direction='horizontal', defer_image=False):
     mirrors the bitmap there, in the recorded order -- bit-identical to the host bitmap path."""
     if direction not in ('horizontal', 'vertical'):
         raise ValueError(f"Invalid flipping direction '{direction}'")
-    h, w = sample['img'].shape[:2]
+    h, w = _frame(sample)
     ax = 1 if direction == 'horizontal' else 0
     out = dict(sample)
+    _resized_needs_deferral(sample, defer_image)
     if defer_image:          # the prefetching loader: the image is mirrored on the device after the upload (to_device_batch)
         out['img_flip'] = tuple(sample.get('img_flip', ())) + (direction,)
     else:
@@ -146,6 +147,106 @@ def flip_sample(sample, direction='horizontal', defer_image=False):
     out['gt_offsets'] = flip_offsets(sample['gt_offsets'], direction)
     out['flip'], out['flip_direction'] = True, direction
     return out
+
+
+# ---- Resize (transforms.py:34-349) and Pad (:560-640) ----------------------------------------------------------------------------
+# The sample-level algebra only: sizes, scale draws, boxes, offsets, meta.  The pixels are resampled on the device, after the upload
+# (kernels.image_resize_prep / mask_resize_u8), so a resized sample keeps its SOURCE image and carries the geometry in 'resize'.
+
+
+def rescale_size(old_size, scale):
+    """mmcv.imrescale's size rule for a tuple scale, from memory of mmcv/image/geometric.py (mmcv is not installed where this
+    was written): (w, h), (a, b) -> (new_w, new_h) with s = min(long / max(h, w), short / min(h, w)) and int(x * s + 0.5)."""
+    w, h = old_size
+    long_edge, short_edge = max(scale), min(scale)
+    s = min(long_edge / max(h, w), short_edge / min(h, w))
+    return int(w * float(s) + 0.5), int(h * float(s) + 0.5)
+
+
+def random_select(img_scales, rng):
+    """Resize.random_select (transforms.py:87-102)."""
+    return img_scales[rng.randint(len(img_scales))]
+
+
+def random_sample(img_scales, rng):
+    """Resize.random_sample (transforms.py:105-129): the long edge is drawn first, then the short edge."""
+    if len(img_scales) != 2:
+        raise ValueError(f"multiscale_mode='range' takes two scales, got {img_scales}")
+    longs, shorts = [max(s) for s in img_scales], [min(s) for s in img_scales]
+    long_edge = rng.randint(min(longs), max(longs) + 1)
+    short_edge = rng.randint(min(shorts), max(shorts) + 1)
+    return int(long_edge), int(short_edge)
+
+
+def random_sample_ratio(img_scale, ratio_range, rng):
+    """Resize.random_sample_ratio (transforms.py:132-156)."""
+    min_ratio, max_ratio = ratio_range
+    if not min_ratio <= max_ratio:
+        raise ValueError(f'ratio_range {ratio_range}: the minimum comes first')
+    ratio = rng.random_sample() * (max_ratio - min_ratio) + min_ratio
+    return int(img_scale[0] * ratio), int(img_scale[1] * ratio)
+
+
+def random_scale(img_scales, multiscale_mode, ratio_range, rng):
+    """Resize._random_scale (transforms.py:158-189).  A single scale without a ratio_range draws nothing."""
+    if ratio_range is not None:
+        return random_sample_ratio(img_scales[0], ratio_range, rng)
+    if len(img_scales) == 1:
+        return tuple(img_scales[0])
+    if multiscale_mode == 'range':
+        return random_sample(img_scales, rng)
+    if multiscale_mode == 'value':
+        return tuple(random_select(img_scales, rng))
+    raise NotImplementedError(f'multiscale_mode={multiscale_mode!r}')
+
+
+def resize_geometry(src_shape, scale, keep_ratio=True, pad_divisor=32):
+    """Resize._resize_img's bookkeeping (transforms.py:191-220) and Pad's (:590-600) for a source of src_shape = (h, w):
+    -> dict(size=(new_h, new_w), pad=(pad_h, pad_w), w_scale, h_scale).  keep_ratio=False is mmcv.imresize: scale is (w, h)."""
+    h, w = src_shape[:2]
+    new_w, new_h = rescale_size((w, h), scale) if keep_ratio else (int(scale[0]), int(scale[1]))
+    if new_w < 1 or new_h < 1:
+        raise ValueError(f'scale {scale} resizes a {w}x{h} image to {new_w}x{new_h}')
+    d = int(pad_divisor) if pad_divisor else 1
+    pad = (int(np.ceil(new_h / d)) * d, int(np.ceil(new_w / d)) * d)
+    return dict(size=(new_h, new_w), pad=pad, w_scale=new_w / w, h_scale=new_h / h, keep_ratio=bool(keep_ratio))
+
+
+def resize_sample(sample, scale, keep_ratio=True, pad_divisor=32):
+    """One training sample under Resize(scale, keep_ratio) followed, at the end of the pipeline, by Pad(size_divisor).  Boxes are
+    multiplied by the float32 scale_factor and clipped to img_shape (_resize_bboxes, transforms.py:222-229).  The image and the
+    bitmaps stay at the source size: 'resize' carries the geometry to ``to_device_batch``.
+
+    DEVIATION: the reference's Resize.__call__ (transforms.py:334-341) never touches ``offset_fields``, so at any scale other
+    than 1 its gt_offsets are not in the resized image's frame.  Here they are multiplied by (w_scale, h_scale)."""
+    if sample.get('gt_masks') is not None:
+        raise NotImplementedError('Resize takes polygon samples (gt_polygons): the bitmaps are rasterised at the source size and '
+                                  'resized on the device')
+    if 'resize' in sample or sample.get('img_flip') or sample.get('flip') or sample.get('rotate'):
+        raise ValueError('Resize comes first in the pipeline: the sample has been resized, flipped or rotated already')
+    g = resize_geometry(sample['img'].shape, scale, keep_ratio, pad_divisor)
+    factor = np.array([g['w_scale'], g['h_scale'], g['w_scale'], g['h_scale']], dtype=np.float32)
+    out = dict(sample)
+    bboxes = np.asarray(sample['gt_bboxes'], np.float32).reshape(-1, 4) * factor
+    bboxes[:, 0::2] = np.clip(bboxes[:, 0::2], 0, g['size'][1])
+    bboxes[:, 1::2] = np.clip(bboxes[:, 1::2], 0, g['size'][0])
+    out['gt_bboxes'] = bboxes
+    out['gt_offsets'] = np.asarray(sample['gt_offsets'], np.float32).reshape(-1, 2) * factor[:2]
+    out['resize'] = g
+    out['img_shape'] = g['size'] + (3,)
+    out['scale_factor'] = factor
+    return out
+
+
+def _frame(sample):
+    """(h, w) of the frame the sample's boxes live in: the resized image's for a resized sample, else the image's own."""
+    return tuple(sample['img_shape'][:2]) if 'resize' in sample else sample['img'].shape[:2]
+
+
+def _resized_needs_deferral(sample, defer_image):
+    if 'resize' in sample and not defer_image:
+        raise ValueError('a resized sample keeps its source pixels: flips and rotations of it are deferred to the device '
+                         '(defer_image=True)')
 
 
 RIGHT_ANGLES = (0, 90, 180, 270)
@@ -281,11 +382,12 @@ def rotate_sample(sample, angle, defer_image=False):
     Angle 0 with rotate=True leaves the pixels alone (nothing is recorded) but, as in the reference, still sends boxes and
     offsets through bbox_rotate / offset_rotate, and ``rotate`` stays True in the meta."""
     angle, = check_rotate_angles((angle,))
-    h, w = sample['img'].shape[:2]
+    h, w = _frame(sample)
     if angle in (90, 270) and h != w:
         raise NotImplementedError(f'RandomRotate by {angle} needs a square tile, got {w}x{h}: the rotated image is not expanded')
     k = -angle // 90
     out = dict(sample)
+    _resized_needs_deferral(sample, defer_image)
     if angle:
         if defer_image:
             out['img_flip'] = tuple(sample.get('img_flip', ())) + (angle,)
@@ -305,9 +407,13 @@ def rotate_sample(sample, angle, defer_image=False):
     return out
 
 
-def _permute_masks(m, ops):
+def _permute_masks(m, ops, resize=None):
     """Rasterised bitmaps [K,H,W] of a polygon sample under its recorded operations.  Flips alone: the mirrored copies as before;
-    a record with a rotation: composed to one element, one launch of loft_mask_d4_u8."""
+    a record with a rotation: composed to one element, one launch of loft_mask_d4_u8.  A resized sample (``resize``: its
+    geometry): nearest-neighbour Resize, the element and Pad in one launch of loft_mask_resize_d4_u8."""
+    if resize is not None:
+        from . import kernels as K
+        return K.mask_resize_u8(m.contiguous(), resize['size'], resize['pad'], d4_compose(ops))
     if not _carries_rotation(ops):
         for d in ops:                                       # flip_sample on a polygon sample: the bitmap is mirrored, as the
             m = m.flip(2 if d == 'horizontal' else 1)       # reference's RandomFlip does after LoadAnnotations rasterised it
@@ -324,7 +430,9 @@ def _masks_of(s, dev):
         from . import kernels as K
         h, w = s['img'].shape[:2]
         m = K.poly2mask(s.get('gt_polygons_packed') or s['gt_polygons'], h, w, device=dev)
-        return _permute_masks(m, s.get('mask_flips', ()))
+        return _permute_masks(m, s.get('mask_flips', ()), s.get('resize'))
+    if 'resize' in s:
+        raise NotImplementedError('Resize takes polygon samples (gt_polygons), not host bitmaps')
     return torch.from_numpy(np.ascontiguousarray(s['gt_masks'], dtype=np.uint8)).to(dev)
 
 
@@ -362,7 +470,17 @@ def to_device_batch(samples, device='cuda', mean=(123.675, 116.28, 103.53), std=
     rgb = [bool(s.get('img_rgb', False)) for s in samples]         # decoded straight to RGB: Normalize's reversal already done
     if not to_rgb and any(rgb):
         raise ValueError('samples decoded to RGB need to_rgb=True (the configured Normalize of bonai_instance.py:3-4)')
-    if any(_carries_rotation(s.get('img_flip', ())) for s in samples):
+    geoms = [s.get('resize') for s in samples]
+    if any(g is not None for g in geoms):
+        # Resize (and Pad): one geometry per batch -- loft_rpn_decode takes one img_shape per batch -- and the whole chain,
+        # Resize, the element of the deferred record, channel order, Normalize, Pad, HWC -> CHW, in one launch
+        if any(g != geoms[0] for g in geoms):
+            raise NotImplementedError('a batch takes ONE scale (per-sample scale draws are not supported): its samples carry '
+                                      f'{sorted({(g["size"], g["pad"]) if g else None for g in geoms}, key=str)}')
+        from . import kernels as K
+        img = K.image_resize_prep(imgs, geoms[0]['size'], geoms[0]['pad'], [d4_compose(s.get('img_flip', ())) for s in samples],
+                                  [r or not to_rgb for r in rgb], mean, std)
+    elif any(_carries_rotation(s.get('img_flip', ())) for s in samples):
         # RandomRotate's image permutation, deferred by the loader: every sample's record of flips and rotations composed to one
         # element, and the whole batch -- permutation, channel order, Normalize, HWC -> CHW -- in one launch
         elems = [d4_compose(s.get('img_flip', ())) for s in samples]
@@ -382,6 +500,10 @@ def to_device_batch(samples, device='cuda', mean=(123.675, 116.28, 103.53), std=
                           flip_direction=s.get('flip_direction'), rotate=bool(s.get('rotate', False)),
                           rotate_angle=int(s.get('rotate_angle', 0)),
                           img_norm_cfg=dict(mean=np.array(mean, np.float32), std=np.array(std, np.float32), to_rgb=to_rgb)))
+        if 'resize' in s:                   # Resize's and Pad's entries (transforms.py:216-220, 597-599)
+            g = s['resize']
+            metas[-1].update(img_shape=g['size'] + (3,), pad_shape=g['pad'] + (3,), scale_factor=s['scale_factor'],
+                             keep_ratio=g['keep_ratio'])
     if dev.type == 'cuda' and staged is not None:
         # the loader's path: every small array of the batch (boxes, labels, offsets, polygon vertices and their offset tables)
         # in ONE pinned buffer and ONE asynchronous copy -- 48 pageable synchronous copies of a few hundred bytes each were
@@ -434,6 +556,6 @@ def _small_arrays_one_copy(samples, dev):
             continue
         h, w = s['img'].shape[:2]
         m = K.poly2mask_device(aux[i]['_xy'], aux[i]['_poff'], aux[i]['_ioff'], packs[i].n, h, w, packs[i].maxv)
-        masks.append(_permute_masks(m, s.get('mask_flips', ())))
+        masks.append(_permute_masks(m, s.get('mask_flips', ()), s.get('resize')))
     out['gt_masks'] = masks
     return out

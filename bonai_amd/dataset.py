@@ -19,7 +19,10 @@ What is mirrored, with the reference's semantics:
   * RandomRotate (transforms.py:1837-2096), optional: probability ``rotate_ratio`` per sample, the angle drawn from
     ``rotate_choice``; right angles on square tiles only, for the reason data.check_rotate_angles gives;
   * Resize / Pad: BONAI tiles are 1024 x 1024, the configured scale is (1024, 1024) with keep_ratio and the pad divisor 32, so both
-    are identities; another tile size raises (the device path takes fixed-size batches).
+    are identities; without ``resize`` another tile size raises (the device path takes fixed-size batches).  ``resize`` (a dict of
+    Resize's arguments) and ``pad_divisor`` run both on the device (bonai_amd/csrc/resize.hip): source tiles of one size, any
+    size; the three scale draws of transforms.py:87-156 -- ONE draw per batch, a deviation: the reference draws per sample;
+    boxes scaled and clipped as _resize_bboxes does; gt_offsets scaled too, which the reference does not do (data.resize_sample);
 Image decoding uses PIL (cv2 / mmcv are not in this image); ``mmcv.imread`` returns BGR, so the RGB decode is reversed to BGR and
 ``to_device_batch(to_rgb=True)`` converts it back exactly as Normalize does.
 
@@ -38,7 +41,8 @@ import os
 
 import numpy as np
 
-from .data import check_rotate_angles, flip_sample, parse_bonai_annotations, rotate_sample, to_device_batch
+from .data import (check_rotate_angles, flip_sample, parse_bonai_annotations, random_scale, resize_geometry, resize_sample, rotate_sample,
+                   to_device_batch)
 
 CLASSES = ('building',)
 
@@ -47,7 +51,8 @@ class BonaiDataset:
     def __init__(self, ann_file, img_prefix='', classes=None, test_mode=False, filter_empty_gt=True, bbox_type='roof',
                  mask_type='roof', offset_coordinate='rectangle', resolution=0.6, ignore_buildings=True, flip_ratio=0.5,
                  flip_direction=('horizontal', 'vertical'), img_scale=(1024, 1024), seed=0, host_rasteriser=None,
-                 rotate_ratio=None, rotate_choice=(0, 90, 180, 270), rotate_first=False, test_views=None):
+                 rotate_ratio=None, rotate_choice=(0, 90, 180, 270), rotate_first=False, test_views=None, resize=None,
+                 pad_divisor=32):
         ann_files = [ann_file] if isinstance(ann_file, str) else list(ann_file)
         prefixes = [img_prefix] * len(ann_files) if isinstance(img_prefix, str) else list(img_prefix)
         if len(prefixes) != len(ann_files):
@@ -95,6 +100,10 @@ class BonaiDataset:
             keep = self._filter_imgs()
             self.data_infos = [self.data_infos[i] for i in keep]
             self.anns = [self.anns[i] for i in keep]
+        # Resize + Pad (transforms.py:34-349, 560-640) on the device; None: tiles have the network's size, as before
+        self.resize, self.pad_divisor, self.tile_size = self._check_resize(resize, pad_divisor), pad_divisor, self.img_scale
+        if self.resize is not None:
+            self._init_resize()
         # custom.py:158-168: group flag by aspect ratio
         self.flag = np.array([1 if d['width'] / d['height'] > 1 else 0 for d in self.data_infos], dtype=np.uint8)
 
@@ -134,6 +143,86 @@ class BonaiDataset:
     def __len__(self):
         return len(self.data_infos)
 
+    # ------------------------------------------------------------------ Resize / Pad
+    @staticmethod
+    def _check_resize(resize, pad_divisor):
+        """Resize's arguments (transforms.py:59-84) as a normalised dict, or None."""
+        if resize is None:
+            return None
+        unknown = set(resize) - {'type', 'img_scale', 'multiscale_mode', 'ratio_range', 'keep_ratio', 'backend', 'interpolation'}
+        if unknown:
+            raise ValueError(f'resize: unknown keys {sorted(unknown)}')
+        if resize.get('backend', 'cv2') != 'cv2' or resize.get('interpolation', 'bilinear') != 'bilinear':
+            raise NotImplementedError("resize: backend='cv2' with bilinear interpolation only (backend='pillow' and other "
+                                      'interpolations are not built)')
+        scales = resize.get('img_scale')
+        scales = [tuple(s) for s in scales] if isinstance(scales, list) else [tuple(scales)] if scales is not None else []
+        if not scales or any(len(s) != 2 or min(s) < 1 for s in scales):
+            raise ValueError(f"resize: img_scale is a (w, h) tuple or a list of them, got {resize.get('img_scale')}")
+        mode, ratio = resize.get('multiscale_mode', 'range'), resize.get('ratio_range')
+        if ratio is not None:
+            if len(scales) != 1:
+                raise ValueError('resize: ratio_range goes with a single img_scale (transforms.py:74-76)')
+            ratio = tuple(ratio)
+        elif mode not in ('value', 'range'):
+            raise ValueError(f"resize: multiscale_mode is 'value' or 'range', got {mode!r}")
+        elif mode == 'range' and len(scales) > 2:
+            raise ValueError("resize: multiscale_mode='range' takes two scales (transforms.py:119)")
+        if pad_divisor not in (None, 0, 1) and (not isinstance(pad_divisor, int) or pad_divisor < 1):
+            raise ValueError(f'pad_divisor is a positive integer or None, got {pad_divisor}')
+        return dict(img_scale=scales, multiscale_mode=mode, ratio_range=ratio, keep_ratio=bool(resize.get('keep_ratio', True)))
+
+    def _init_resize(self):
+        if self.host_rasteriser is not None:
+            raise NotImplementedError('resize: bitmaps are rasterised on the device at the source size and resized there; '
+                                      'host_rasteriser is not supported together with it')
+        if self.test_views is not None:
+            raise NotImplementedError('resize together with test_views (a resized view together with flips or rotations, or more '
+                                      'than one scale at test time) is not supported')
+        if self.test_mode:
+            if self.multi_scale:
+                raise NotImplementedError(f"multi-scale test views are not supported: resize {self.resize['img_scale']}, "
+                                          f"ratio_range {self.resize['ratio_range']} can draw more than one size")
+            return
+        # training: one source size per dataset (the prefetcher's staging slots are sized by it)
+        sizes = {(d['width'], d['height']) for d in self.data_infos}
+        if len(sizes) > 1:
+            first = (self.data_infos[0]['width'], self.data_infos[0]['height'])
+            odd = next(d for d in self.data_infos if (d['width'], d['height']) != first)
+            raise NotImplementedError(f"{odd['filename']}: {odd['width']}x{odd['height']} tile in a dataset of {first[0]}x{first[1]} "
+                                      'tiles; datasets with mixed source sizes are not supported in training')
+        if sizes:
+            self.tile_size = next(iter(sizes))
+        if self.rotate_ratio and any(a in (90, 270) for a in self.rotate_choice) and \
+                (self.tile_size[0] != self.tile_size[1] or not self.resize['keep_ratio']):
+            raise NotImplementedError('RandomRotate by 90 / 270 after Resize needs a square target: square source tiles and '
+                                      f"keep_ratio=True, got {self.tile_size} tiles, keep_ratio={self.resize['keep_ratio']}")
+        if not self.multi_scale:
+            self._geometry(self.resize['img_scale'][0])           # a fixed scale is checked now, a drawn one when it is drawn
+
+    @property
+    def multi_scale(self):
+        """True when ``resize`` can draw more than one size."""
+        return self.resize is not None and (self.resize['ratio_range'] is not None or len(set(self.resize['img_scale'])) > 1)
+
+    def draw_scale(self):
+        """Resize._random_scale, ONCE PER BATCH (the reference draws per sample; loft_rpn_decode takes one img_shape per batch).
+        Drawn from the dataset's RandomState before the batch's flip draws; a single scale, or no ``resize``, draws nothing."""
+        if self.resize is None:
+            return None
+        r = self.resize
+        return random_scale(r['img_scale'], r['multiscale_mode'], r['ratio_range'], self.rng)
+
+    def _geometry(self, scale, src_shape=None):
+        """resize_geometry of a scale on this dataset's tiles; refuses a padded side that is a multiple of 32 but not of 64."""
+        h, w = src_shape if src_shape is not None else self.tile_size[::-1]
+        g = resize_geometry((h, w), scale, self.resize['keep_ratio'], self.pad_divisor)
+        if any(p % 64 for p in g['pad']):
+            raise NotImplementedError(f"scale {tuple(scale)} on {w}x{h} tiles pads to {g['pad'][1]}x{g['pad'][0]}: the model has "
+                                      'only been exercised on tiles whose sides are multiples of 64 (an odd P5 level is untested); '
+                                      'use pad_divisor=64')
+        return g
+
     def get_ann_info(self, idx):
         """bonai.py:105-256 on image ``idx``.  Parsed once and kept (the reference parses on every access; the result is a pure
         function of the annotation file): the loader reads it twice per sample -- resolve() and prepare_train_img()."""
@@ -150,7 +239,7 @@ class BonaiDataset:
         rgb = np.asarray(Image.open(path).convert('RGB'))
         return np.ascontiguousarray(rgb[:, :, ::-1])                    # BGR, as mmcv.imread / cv2 deliver it
 
-    def prepare_train_img(self, idx, flip_draw=None, img_out=None, decode=True, rotate_angle='draw'):
+    def prepare_train_img(self, idx, flip_draw=None, img_out=None, decode=True, rotate_angle='draw', scale=None):
         """One training sample.  flip_draw: the uniform draw that decides the flip (None: drawn here from self.rng).
         rotate_angle: RandomRotate's decision -- an angle, None for "not rotated", 'draw': drawn here (resolve_all's order).
         decode=False (with img_out): everything but the pixels -- a decoder process fills img_out (decode_tile_into).
@@ -158,7 +247,9 @@ class BonaiDataset:
         there with ONE copy and nothing else touches the pixels on the host: the sample says ``img_rgb`` (no BGR round trip:
         to_device_batch skips Normalize's to_rgb reversal) and ``img_flip`` (RandomFlip's mirror of the image happens on the
         device after the upload) -- same device values as the host path, a third of the host work and of the time spent holding
-        the interpreter lock next to the training loop."""
+        the interpreter lock next to the training loop.
+        scale: the batch's Resize scale (draw_scale); with it the pixels stay at the source size and every image operation is
+        deferred to the device."""
         info = self.data_infos[idx]
         ann = self.get_ann_info(idx)
         if ann['bboxes'].shape[0] == 0:                                 # custom.py:188-191: no gt after parsing -> another sample
@@ -178,7 +269,13 @@ class BonaiDataset:
             else:
                 img = np.asarray(im)
         h, w = img.shape[:2]
-        if (h, w) != self.img_scale[::-1] or h % 32 or w % 32:
+        if self.resize is not None:
+            if scale is None:
+                raise ValueError('a dataset with resize takes the scale of the batch (draw_scale)')
+            if (w, h) != self.tile_size:
+                raise NotImplementedError(f"{info['filename']}: {w}x{h} tile in a dataset of {self.tile_size[0]}x{self.tile_size[1]} "
+                                          'tiles; datasets with mixed source sizes are not supported in training')
+        elif (h, w) != self.img_scale[::-1] or h % 32 or w % 32:
             raise NotImplementedError(f"{info['filename']}: {w}x{h} tile; the device path takes the dataset's {self.img_scale} "
                                       'tiles as they are (Resize / Pad of bonai_instance.py:11,14 are identities there)')
         sample = dict(img=img, filename=info['filename'], gt_bboxes=ann['bboxes'], gt_labels=ann['labels'],
@@ -195,14 +292,19 @@ class BonaiDataset:
                 sample['gt_polygons_packed'] = pk
         else:
             sample['gt_masks'] = np.stack([self.host_rasteriser(m, h, w) for m in ann['masks']])
+        defer = img_out is not None
+        if self.resize is not None:
+            self._geometry(scale)
+            sample = resize_sample(sample, scale, self.resize['keep_ratio'], self.pad_divisor)
+            defer = True
         for transform in ('rotate', 'flip') if self.rotate_first else ('flip', 'rotate'):
             if transform == 'flip':
                 if self.flip_ratio and (self.rng.rand() if flip_draw is None else flip_draw) < self.flip_ratio:
-                    sample = flip_sample(sample, self.flip_direction, defer_image=img_out is not None)
+                    sample = flip_sample(sample, self.flip_direction, defer_image=defer)
             elif self.rotate_ratio:
                 angle = self._draw_rotate() if isinstance(rotate_angle, str) else rotate_angle
                 if angle is not None:
-                    sample = rotate_sample(sample, angle, defer_image=img_out is not None)
+                    sample = rotate_sample(sample, angle, defer_image=defer)
         return sample
 
     def _draw_rotate(self):
@@ -244,8 +346,11 @@ class BonaiDataset:
         if self.test_mode:
             info = self.data_infos[idx]
             return dict(img=self._read_image(info), filename=info['filename'])
+        return self._train_sample(idx, self.draw_scale())
+
+    def _train_sample(self, idx, scale):
         idx, draw, angle = self.resolve_all(idx)
-        return self.prepare_train_img(idx, flip_draw=draw, rotate_angle=angle)
+        return self.prepare_train_img(idx, flip_draw=draw, rotate_angle=angle, scale=scale)
 
     # ------------------------------------------------------------------ batches
     def epoch_indices(self, epoch, samples_per_gpu, rank=0, world=1, shuffle=True, seed=0):
@@ -270,7 +375,11 @@ class BonaiDataset:
         groups = [idx[i:i + samples_per_gpu] for i in range(0, len(idx), samples_per_gpu)]
         if prefetch <= 0 or self.test_mode:
             for g in groups:
-                yield to_device_batch([self[j] for j in g], device=device)
+                if self.resize is None or self.test_mode:
+                    yield to_device_batch([self[j] for j in g], device=device)
+                else:
+                    scale = self.draw_scale()                  # one scale per batch, before the batch's flip draws
+                    yield to_device_batch([self._train_sample(j, scale) for j in g], device=device)
             return
         yield from _Prefetcher(self, groups, device, depth=prefetch, workers=workers, processes=processes)
 
@@ -365,10 +474,22 @@ class BonaiDataset:
             if self.test_views is not None:
                 yield i, self._view_batch(info, device)
                 continue
+            if self.resize is not None:
+                yield i, self._resized_batch(info, device)
+                continue
             b = to_device_batch([dict(img=self._read_image(info), filename=info['filename'], gt_bboxes=np.zeros((0, 4), np.float32),
                                       gt_labels=np.zeros((0,), np.int64), gt_masks=np.zeros((0, 1, 1), np.uint8),
                                       gt_offsets=np.zeros((0, 2), np.float32))], device=device)
             yield i, dict(img=[b['img']], img_metas=[b['img_metas']])
+
+    def _resized_batch(self, info, device):
+        """One tile of any size under the test pipeline's Resize and Pad: the resized, padded view with its meta."""
+        img = self._read_image(info)
+        sample = dict(img=img, filename=info['filename'], gt_bboxes=np.zeros((0, 4), np.float32), gt_labels=np.zeros((0,), np.int64),
+                      gt_polygons=[], gt_offsets=np.zeros((0, 2), np.float32))
+        self._geometry(self.resize['img_scale'][0], img.shape[:2])
+        b = to_device_batch([resize_sample(sample, self.resize['img_scale'][0], self.resize['keep_ratio'], self.pad_divisor)], device=device)
+        return dict(img=[b['img']], img_metas=[b['img_metas']])
 
     def _view_batch(self, info, device, mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375)):
         """One tile under ``test_views``: the tile goes up once as uint8 and ALL V view images come from one image_prep_d4 launch
@@ -447,7 +568,7 @@ class _Prefetcher:
         self.workers = max(1, int(workers))
         self.processes = self.cuda if processes is None else bool(processes)
         bs = max(len(g) for g in groups) if groups else 0
-        w, h = ds.img_scale
+        w, h = ds.tile_size
         # ring of staging buffers: depth in the queue + one being filled + one the consumer's upload may still read
         self.slots, self.shm = [], None
         nslots = self.depth + 2
@@ -488,15 +609,16 @@ class _Prefetcher:
                     # loaders emit the same stream
                     futs, samples = [], []
                     h, w = buf.shape[1:3]
+                    scale = self.ds.draw_scale()                   # Resize: one scale per batch, before the batch's flip draws
                     for i, j in enumerate(g):
                         j, draw, angle = self.ds.resolve_all(j)
                         if self.processes:
                             info = self.ds.data_infos[j]
                             futs.append(pool.submit(decode_tile_into, os.path.join(info['_prefix'], info['filename']), self.shm.name,
                                                     k * self.slot_bytes + i * h * w * 3, h, w))
-                            samples.append(self.ds.prepare_train_img(j, draw, buf[i], decode=False, rotate_angle=angle))
+                            samples.append(self.ds.prepare_train_img(j, draw, buf[i], decode=False, rotate_angle=angle, scale=scale))
                         else:
-                            futs.append(pool.submit(self.ds.prepare_train_img, j, draw, buf[i], True, angle))
+                            futs.append(pool.submit(self.ds.prepare_train_img, j, draw, buf[i], True, angle, scale))
                     if self.processes:
                         for f in futs:
                             err = f.result()

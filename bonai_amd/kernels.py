@@ -1660,6 +1660,103 @@ def mask_d4(masks_u8, elem):
     return out
 
 
+def _linear_axis(S, D):
+    """One axis of the bilinear rule of include/loft_hip.h (loft_image_resize_prep_d4): first tap int32 [D], coefficients int16
+    [D,2].  float64 for the scale and the sample position, float32 from the cast on, as the header states it."""
+    f = ((np.arange(D, dtype=np.float64) + 0.5) * (np.float64(S) / np.float64(D)) - 0.5).astype(np.float32)
+    s = np.floor(f).astype(np.int32)
+    f = f - s.astype(np.float32)
+    f[s < 0] = 0
+    s[s < 0] = 0
+    f[s >= S - 1] = 0
+    s[s >= S - 1] = S - 1
+    coef = np.stack([np.rint((np.float32(1) - f) * np.float32(2048)), np.rint(f * np.float32(2048))], axis=1).astype(np.int16)
+    return s, coef
+
+
+def _nearest_axis(S, D):
+    """One axis of the nearest-neighbour rule (loft_mask_resize_d4_u8): source index int32 [D], in float64."""
+    return np.minimum(np.floor(np.arange(D, dtype=np.float64) * (1.0 / (D / S))), S - 1).astype(np.int32)
+
+
+def resize_tables(Hs, Ws, Hd, Wd):
+    """The host tables of the two resize kernels for one (source size, target size), numpy only: xofs / yofs int32, xcoef / ycoef
+    int16 [.,2] (bilinear, image) and xidx / yidx int32 (nearest, bitmaps)."""
+    if min(Hs, Ws, Hd, Wd) < 1:
+        raise ValueError(f'resize_tables: sizes are positive, got {Ws}x{Hs} -> {Wd}x{Hd}')
+    xofs, xcoef = _linear_axis(Ws, Wd)
+    yofs, ycoef = _linear_axis(Hs, Hd)
+    return dict(xofs=xofs, xcoef=xcoef, yofs=yofs, ycoef=ycoef, xidx=_nearest_axis(Ws, Wd), yidx=_nearest_axis(Hs, Hd))
+
+
+_RESIZE_TABLES = {}
+
+
+def _resize_tables_device(Hs, Ws, Hd, Wd, device):
+    """resize_tables on the device, uploaded once per (source size, target size, device) and kept.  The upload is complete when
+    this returns: the cached tables are read from whichever stream calls next (the loader's side stream and the caller's)."""
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    key = (Hs, Ws, Hd, Wd, device.index)
+    t = _RESIZE_TABLES.get(key)
+    if t is None:
+        if len(_RESIZE_TABLES) >= 64:                     # ratio_range draws many sizes: bounded, rebuilt on demand
+            _RESIZE_TABLES.clear()
+        t = {k: torch.from_numpy(np.ascontiguousarray(v)).to(device) for k, v in resize_tables(Hs, Ws, Hd, Wd).items()}
+        torch.cuda.current_stream(device).synchronize()
+        _RESIZE_TABLES[key] = t
+    return t
+
+
+def image_resize_prep(imgs_u8, size, pad_shape, elems, channels_kept, mean, std):
+    """loft_image_resize_prep_d4: uint8 [n,Hs,Ws,3] device tensor -> fp32 [n,3,Hp,Wp]: every image resized to ``size`` = (Hd, Wd)
+    (bilinear, the integer rule of include/loft_hip.h), put under its element ``elems[i]``, normalised as image_prep_d4 does, and
+    laid on a zero canvas ``pad_shape`` = (Hp, Wp).  One launch."""
+    lib = L.load()
+    L.dev_check(imgs_u8)
+    if imgs_u8.dtype != torch.uint8 or imgs_u8.dim() != 4 or imgs_u8.shape[3] != 3 or not imgs_u8.is_contiguous():
+        raise L.LoftHipError(f'image_resize_prep takes a contiguous uint8 [n,H,W,3] tensor, got {imgs_u8.dtype} {tuple(imgs_u8.shape)}')
+    n, Hs, Ws, _ = imgs_u8.shape
+    (Hd, Wd), (Hp, Wp) = (int(v) for v in size), (int(v) for v in pad_shape)
+    if len(elems) != n or len(channels_kept) != n or any(e & ~7 for e in elems):
+        raise L.LoftHipError('image_resize_prep: one element (0..7) and one channel flag per sample')
+    if Hd > Hp or Wd > Wp:
+        raise L.LoftHipError(f'image_resize_prep: the {Wd}x{Hd} image does not fit the {Wp}x{Hp} canvas')
+    if Hd != Wd and any(e & D4_TRANSPOSE for e in elems):
+        raise L.LoftHipError(f'image_resize_prep: a transposing element needs a square target, got {Wd}x{Hd}')
+    tb = _resize_tables_device(Hs, Ws, Hd, Wd, imgs_u8.device)
+    table = h2d([int(e) | (D4_CHANNELS_KEPT if k else 0) for e, k in zip(elems, channels_kept)], torch.int32, imgs_u8.device)
+    out = torch.empty(n, 3, Hp, Wp, dtype=torch.float32, device=imgs_u8.device)
+    L.check(lib.loft_image_resize_prep_d4(L.ptr(imgs_u8), L.ptr(table), n, Hs, Ws, Hd, Wd, L.ptr(tb['xofs']), L.ptr(tb['xcoef']),
+                                          L.ptr(tb['yofs']), L.ptr(tb['ycoef']), Hp, Wp, int(any(e & D4_TRANSPOSE for e in elems)),
+                                          mean[0], mean[1], mean[2], std[0], std[1], std[2], L.ptr(out), L.stream()),
+            'loft_image_resize_prep_d4')
+    return out
+
+
+def mask_resize_u8(masks_u8, size, pad_shape, elem=0):
+    """loft_mask_resize_d4_u8: uint8 [K,Hs,Ws] device bitmaps -> uint8 [K,Hp,Wp]: nearest-neighbour resize to ``size`` = (Hd, Wd),
+    one element (D4_* bits), zero padding to ``pad_shape`` = (Hp, Wp).  A new tensor."""
+    lib = L.load()
+    L.dev_check(masks_u8)
+    if masks_u8.dtype != torch.uint8 or masks_u8.dim() != 3 or not masks_u8.is_contiguous():
+        raise L.LoftHipError(f'mask_resize_u8 takes a contiguous uint8 [K,H,W] tensor, got {masks_u8.dtype} {tuple(masks_u8.shape)}')
+    K_, Hs, Ws = masks_u8.shape
+    (Hd, Wd), (Hp, Wp) = (int(v) for v in size), (int(v) for v in pad_shape)
+    if Hd > Hp or Wd > Wp or Wp % 4:
+        raise L.LoftHipError(f'mask_resize_u8: a {Wd}x{Hd} bitmap on a {Wp}x{Hp} canvas (the canvas width is a multiple of 4)')
+    if int(elem) & ~7 or (Hd != Wd and int(elem) & D4_TRANSPOSE):
+        raise L.LoftHipError(f'mask_resize_u8: element {elem} on a {Wd}x{Hd} target')
+    out = torch.empty(K_, Hp, Wp, dtype=torch.uint8, device=masks_u8.device)
+    if K_ == 0:
+        return out
+    tb = _resize_tables_device(Hs, Ws, Hd, Wd, masks_u8.device)
+    L.check(lib.loft_mask_resize_d4_u8(L.ptr(masks_u8), K_, Hs, Ws, Hd, Wd, L.ptr(tb['xidx']), L.ptr(tb['yidx']), Hp, Wp, int(elem),
+                                       L.ptr(out), L.stream()), 'loft_mask_resize_d4_u8')
+    return out
+
+
 class PackedPolygons:
     """The host arrays loft_poly2mask reads (vertices fp64 [V,2], polygon offsets, instance offsets): built once per annotation
     (pack_polygons) and reusable -- the loader caches it per image instead of re-walking ~100 python lists every epoch."""

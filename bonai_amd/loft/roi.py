@@ -809,7 +809,13 @@ class LoftRoIHead(nn.Module):
                     segm = list(pasted.bool().cpu().numpy())
             segm_results = results_by_class(segm, dl, ncls)
         offset_pred = self._offset_forward(x, det_rois)
-        if views is None:
+        if views is None and sf is not None and cfg.get('rescale_offsets', False):
+            # opt-in: get_offsets ignores scale_factor, as the reference's does, and returns pixels of the network input; with it
+            # the offsets are divided by (w_scale, h_scale) like the boxes, so that boxes, masks and offsets (and the footprints
+            # pasted through the device offsets) share the source frame
+            dev = self.offset_head.get_offsets_device(offset_pred, boxes.contiguous(), (1024, 1024)).float() / sf[:2]
+            offset_results = _offsets_out(dev, footprints)
+        elif views is None:
             offset_results = self.offset_head.get_offsets(offset_pred, boxes.contiguous(), meta['scale_factor'], sf is not None,
                                                           with_device=footprints)
         else:

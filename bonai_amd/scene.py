@@ -97,6 +97,11 @@ class SceneDetector:
         if views is None and tcfg.get('pipeline'):
             from .tta import views_from_pipeline
             views = views_from_pipeline(tcfg['pipeline'], self.tile)
+        if tcfg.get('pipeline'):
+            from .tta import resize_from_pipeline
+            if resize_from_pipeline(tcfg['pipeline'], tuple(tcfg.get('img_scale', (1024, 1024)))[::-1]) is not None:
+                raise NotImplementedError('Resize inside SceneDetector is not supported: the test pipeline resizes the tiles; whole-scene '
+                                          'inference cuts tiles of the network\'s size from the scene as it is')
         if views is not None and len(views) > 1:
             raise ValueError(f'the model is configured for test-time augmentation (views {views}): whole-scene inference runs the '
                              'plain tile; drop the flip / rotate_angles of the test pipeline')

@@ -89,6 +89,31 @@ def views_from_pipeline(pipeline, tile=(1024, 1024)):
     return make_views(dirs, angles, tile)
 
 
+def resize_from_pipeline(pipeline, tile=(1024, 1024)):
+    """cfg.data.test.pipeline -> BonaiDataset's ``resize`` / ``pad_divisor`` arguments when its MultiScaleFlipAug entry resizes the
+    dataset's tiles (``tile`` = (h, w)): flip=False and a single img_scale other than the tile.  None: the tiles are taken as they
+    are.  More than one scale, a scale_factor, or a resized view together with flips or rotations raises."""
+    aug = next((p for p in (pipeline or ()) if p.get('type') == 'MultiScaleFlipAug'), None)
+    if aug is None:
+        return None
+    scale, factor = aug.get('img_scale'), aug.get('scale_factor')
+    scales = list(scale) if isinstance(scale, list) else [] if scale is None else [scale]
+    factors = list(factor) if isinstance(factor, (list, tuple)) else [] if factor is None else [factor]
+    if len(scales) > 1 or len(factors) > 1:
+        raise NotImplementedError(f'MultiScaleFlipAug img_scale={scale} scale_factor={factor}: multi-scale test views are not supported')
+    if factors and float(factors[0]) != 1.0:
+        raise NotImplementedError(f'MultiScaleFlipAug scale_factor={factor}: give the resized size as img_scale')
+    inner = aug.get('transforms') or ()
+    divisor = next((p.get('size_divisor') for p in inner if p.get('type') == 'Pad'), None)
+    keep_ratio = next((p.get('keep_ratio', True) for p in inner if p.get('type') == 'Resize'), True)
+    fits = not divisor or not (tile[0] % divisor or tile[1] % divisor)
+    if (not scales or (tuple(scales[0]) in (tuple(tile), tuple(tile)[::-1]) and keep_ratio)) and fits:
+        return None
+    if aug.get('flip', False) or aug.get('rotate_angles'):
+        raise NotImplementedError('a resized test view together with flips or rotations is not supported')
+    return dict(resize=dict(img_scale=tuple(scales[0]) if scales else tuple(tile)[::-1], keep_ratio=keep_ratio), pad_divisor=divisor)
+
+
 def view_meta(meta, op):
     """The img_meta of one view: the tile's meta with flip / flip_direction / rotate / rotate_angle as the train loader records
     them, the composed element under META_KEY, and the view's own img_shape."""

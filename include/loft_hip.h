@@ -664,6 +664,30 @@ int loft_image_prep_d4(const uint8_t* img, const int32_t* elems, int n, int H, i
                        float mean2, float std0, float std1, float std2, float* out, void* stream);
 int loft_mask_d4_u8(const uint8_t* masks, int K, int H, int W, int elem, uint8_t* out, void* stream);
 
+/* ---- Resize and Pad in front of the symmetries (bonai_amd/csrc/resize.hip) --------------------------------------------------------
+ * mmdet's Resize (transforms.py:34-349) and Pad (:560-640) fused with loft_image_prep_d4 / loft_mask_d4_u8: a source of Hs x Ws is
+ * resized to Hd x Wd, the element is applied to the RESIZED image (the reference flips and rotates after Resize), and the result sits
+ * at the top left of an Hp x Wp canvas whose remaining pixels are zero (Pad's pad_val = 0 after Normalize).  One source size and one
+ * target size per launch; no resized image is written to memory.  All tables are DEVICE arrays built by the host.
+ * loft_image_resize_prep_d4: img uint8 [n,Hs,Ws,3], elems as loft_image_prep_d4 takes them, out fp32 [n,3,Hp,Wp].  The resized
+ *   pixel is the project's statement of cv2.resize(INTER_LINEAR) on 8-bit images, in integers:
+ *     column dx: fx = float32((dx + 0.5) * (Ws / Wd) - 0.5), sx = floor(fx), fx -= sx; sx < 0: sx = 0, fx = 0; sx >= Ws - 1:
+ *       sx = Ws - 1, fx = 0; xofs[dx] = sx, xcoef[dx] = { rint((1 - fx) * 2048), rint(fx * 2048) } as int16 (half to even); the
+ *       second tap is pixel min(sx + 1, Ws - 1).  Rows alike (yofs int32 [Hd], ycoef int16 [Hd][2]).
+ *     S = v[sx] * a0 + v[sx + 1] * a1 on the two tap rows, out = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2.
+ *     Ws == 2 * Wd and Hs == 2 * Hd: out = (v00 + v01 + v10 + v11 + 2) >> 2 instead (the tables are then not read).
+ *   NOT run against OpenCV: the rule is written from memory of its resize.cpp and is this project's definition.
+ *   The resized byte then goes through the Normalize statement of loft_image_prep_d4.  any_transpose as there; a transposing
+ *   element needs Hd == Wd.  Returns hipErrorInvalidValue without launching unless Hd <= Hp and Wd <= Wp.
+ * loft_mask_resize_d4_u8: masks uint8 [K,Hs,Ws] -> out uint8 [K,Hp,Wp] under ONE element, nearest neighbour (BitmapMasks.rescale /
+ *   .resize): out pixel (dy, dx) of the resized bitmap is source pixel (yidx[dy], xidx[dx]), xidx[dx] = min(floor(dx * (1.0 /
+ *   (Wd / Ws))), Ws - 1) in fp64 (int32 [Wd], [Hd]).  Wp % 4 == 0; out must not alias masks. */
+int loft_image_resize_prep_d4(const uint8_t* img, const int32_t* elems, int n, int Hs, int Ws, int Hd, int Wd, const int32_t* xofs,
+                              const int16_t* xcoef, const int32_t* yofs, const int16_t* ycoef, int Hp, int Wp, int any_transpose,
+                              float mean0, float mean1, float mean2, float std0, float std1, float std2, float* out, void* stream);
+int loft_mask_resize_d4_u8(const uint8_t* masks, int K, int Hs, int Ws, int Hd, int Wd, const int32_t* xidx, const int32_t* yidx,
+                           int Hp, int Wp, int elem, uint8_t* out, void* stream);
+
 /* ---- test-time augmentation over the square's symmetries (bonai_amd/csrc/tta.hip) ---------------------------------------------------
  * The merges of mmdet/core/post_processing/merge_augs.py and the aug_test_* mixins for V views of ONE tile, V <= 8.  views: DEVICE
  * int32 [V], one LOFT_D4_* element per view; img_h x img_w: the original tile (a transposing view's image is img_w x img_h).  A box

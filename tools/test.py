@@ -101,7 +101,16 @@ def main():
         from bonai_amd import evaluation as E
         from bonai_amd.dataset import BonaiDataset
         extra = {k: tcfg[k] for k in ('bbox_type', 'mask_type', 'offset_coordinate', 'resolution', 'classes') if k in tcfg}
-        ds = BonaiDataset(ann, prefix, test_mode=True, test_views=views, **extra)
+        resized = tta.resize_from_pipeline(tcfg.get('pipeline'), tile) or {}
+        if resized:
+            if args.tta:
+                raise SystemExit('--tta together with a test pipeline that resizes is refused: a resized view together with flips or '
+                                 'rotations is not supported')
+            # rescale=True semantics: boxes, masks and -- with rescale_offsets -- offsets land in the source frame
+            model.roi_head.test_cfg['rescale_offsets'] = True
+            print(f"test pipeline resizes to {resized['resize']['img_scale']}: test_cfg.rcnn.rescale_offsets = True (offsets are "
+                  'divided by the scale factor, like the boxes)', flush=True)
+        ds = BonaiDataset(ann, prefix, test_mode=True, test_views=views, **resized, **extra)
         coco = None
         if args.coco_ap:
             from bonai_amd.coco_eval import CocoEvaluator

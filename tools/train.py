@@ -67,6 +67,26 @@ def augment_kwargs(pipeline):
     return kw
 
 
+def resize_kwargs(pipeline, tile=(1024, 1024)):
+    """BonaiDataset's ``resize`` / ``pad_divisor`` from the pipeline's Resize and Pad entries.  A Resize that is an identity on the
+    dataset's tiles (one keep_ratio scale equal to the tile, no ratio_range) with a Pad divisor that divides the tile is passed as
+    nothing at all: the loader then runs exactly as it did before Resize existed."""
+    rs = next((p for p in pipeline if p.get('type') == 'Resize'), None)
+    pad = next((p for p in pipeline if p.get('type') == 'Pad'), None)
+    if pad is not None and pad.get('size') is not None:
+        raise NotImplementedError("Pad(size=...) is not supported: give size_divisor")
+    divisor = (pad or {}).get('size_divisor')
+    if rs is not None:
+        scales = rs.get('img_scale')
+        scales = list(scales) if isinstance(scales, list) else [scales]
+        identity = rs.get('ratio_range') is None and len(scales) == 1 and scales[0] is not None and \
+            tuple(scales[0]) in (tuple(tile), tuple(tile)[::-1]) and rs.get('keep_ratio', True) and \
+            not (divisor and (tile[0] % divisor or tile[1] % divisor))
+        if not identity:
+            return dict(resize={k: v for k, v in rs.items() if k != 'type'}, pad_divisor=divisor)
+    return {}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('config')
@@ -145,7 +165,11 @@ def main():
                      if k in tcfg}                     # (bonai.py:18-35: the dataset's own keyword arguments)
             dataset = BonaiDataset(tcfg['ann_file'], tcfg.get('img_prefix', ''), bbox_type=tcfg.get('bbox_type', 'roof'),
                                    mask_type=tcfg.get('mask_type', 'roof'), seed=args.seed + rank,
-                                   **augment_kwargs(tcfg.get('pipeline', [])), **extra)
+                                   **augment_kwargs(tcfg.get('pipeline', [])),
+                                   **resize_kwargs(tcfg.get('pipeline', []), tuple(tcfg.get('img_scale', (1024, 1024)))), **extra)
+            if args.graph and dataset.multi_scale:
+                raise SystemExit('--graph together with a Resize that can draw more than one size is refused: the captured backbone + '
+                                 'neck graphs hold one input shape.  Train without --graph, or with a single img_scale.')
             ipe = args.iters_per_epoch or max(1, len(dataset.epoch_indices(0, bs, rank, world)) // bs)
         elif rank == 0:
             print(f'dataset files of cfg.data.train not found ({files[:1]}...): synthetic tiles', flush=True)
