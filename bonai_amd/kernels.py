@@ -1851,6 +1851,86 @@ def batched_nms(boxes, scores, idxs, nms_cfg, class_agnostic=False):
     return torch.cat([boxes[keep], dets[:, -1:]], dim=-1), keep
 
 
+def multiclass_nms_batched(bboxes, scores, roi_off, score_thr, nms_cfg, max_per_img):
+    """mmdet's multiclass_nms (bbox_nms.py:5-69) for the B images of a batch, nothing read back (csrc/detect.hip): scores fp32
+    [R, C+1] (softmax, background last), bboxes fp32 [R, 4C] or [R, 4]; roi_off: the B+1 row offsets of the images, [0] = 0 and
+    [B] = R -- a host sequence (uploaded here), or a device int64 tensor (then read once, for the launch bounds).
+    -> (dets fp32 [B, max_per_img, 5], labels int64 [B, max_per_img], counts int64 [B] (device), rois fp32 [B * max_per_img, 5]):
+    image b's detections are dets[b, :counts[b]] in the order LoftRoIHead.multiclass_nms gives them (score descending, ties by
+    ascending row * C + class), rows past the count are zero; rois holds (image, box) of all detections image-major without gaps,
+    zeros past sum(counts).  Scores are probabilities: a candidate's must exceed -1."""
+    lib = L.load()
+    cfg = dict(nms_cfg)
+    typ = cfg.pop('type', 'nms')
+    if typ != 'nms':
+        raise L.LoftHipError(f"multiclass_nms_batched: nms type '{typ}' is sequential per image; only type='nms' runs for a batch")
+    if cfg.pop('class_agnostic', False):
+        raise L.LoftHipError('multiclass_nms_batched: class_agnostic=True suppresses across classes; its segments are (image, class)')
+    max_per_img = int(max_per_img)
+    if max_per_img <= 0 or max_per_img > TOPK_MAX:
+        raise L.LoftHipError(f'multiclass_nms_batched: max_per_img = {max_per_img} outside 1 .. {TOPK_MAX} (kernels.TOPK_MAX)')
+    L.dev_check(bboxes, scores)
+    dev = scores.device
+    offs = [int(v) for v in (roi_off.tolist() if torch.is_tensor(roi_off) else roi_off)]
+    R, C = int(scores.shape[0]), int(scores.shape[1]) - 1
+    B = len(offs) - 1
+    if B < 1 or C < 1 or offs[0] != 0 or offs[-1] != R or any(a > b for a, b in zip(offs, offs[1:])):
+        raise L.LoftHipError(f'multiclass_nms_batched: roi_off {offs} does not cut the {R} rows of scores {tuple(scores.shape)} into images')
+    box_cols = int(bboxes.shape[1]) if bboxes.dim() == 2 else -1
+    if bboxes.shape[0] != R or box_cols not in (4, 4 * C):
+        raise L.LoftHipError(f'multiclass_nms_batched: bboxes {tuple(bboxes.shape)} for scores {tuple(scores.shape)}: [R, 4C] or [R, 4] needed')
+    rows = [b - a for a, b in zip(offs, offs[1:])]
+    if max(rows) > NMS_MAX_SEGMENT:
+        raise L.LoftHipError(f'multiclass_nms_batched: an image of {max(rows)} rows can give a segment beyond NMS_MAX_SEGMENT = '
+                             f'{NMS_MAX_SEGMENT} (kernels.NMS_MAX_SEGMENT)')
+    if R * C >= 2 ** 31:
+        raise L.LoftHipError(f'multiclass_nms_batched: {R} rows x {C} classes: flat indices are 32-bit')
+    scores, bboxes = scores.float().contiguous(), bboxes.float().contiguous()
+    if torch.is_tensor(roi_off):
+        L.dev_check(roi_off)
+        roi_off_d = roi_off.to(torch.int64).contiguous()
+        img_off = roi_off_d * C
+    else:
+        tab = h2d(offs + [o * C for o in offs], torch.int64, dev)
+        roi_off_d, img_off = tab[:B + 1], tab[B + 1:]
+    S, cap = B * C, R * C
+    work = torch.empty(2 * S, dtype=torch.int32, device=dev)
+    seg_off = torch.empty(S + 2, dtype=torch.int64, device=dev)
+    img_max = torch.empty(B, dtype=torch.float32, device=dev)
+    flag = torch.empty(cap, dtype=torch.uint8, device=dev)
+    score_flat = torch.empty(cap, dtype=torch.float32, device=dev)
+    cand_score = torch.empty(cap, dtype=torch.float32, device=dev)
+    cand_flat = torch.empty(cap, dtype=torch.int32, device=dev)
+    L.check(lib.loft_det_candidates(L.ptr(scores), L.ptr(bboxes), box_cols, L.ptr(roi_off_d), B, C, R, float(score_thr), L.ptr(work),
+                                    L.ptr(seg_off), L.ptr(img_max), L.ptr(flag), L.ptr(score_flat), L.ptr(cand_score),
+                                    L.ptr(cand_flat), L.stream()), 'loft_det_candidates')
+    # stable descending inside every (image, class) segment; the S + 1st segment is the unused rest of the arrays
+    _, sorted_flat = segmented_sort_desc(cand_score, seg_off, cand_flat)
+    boxes_sorted = torch.empty(cap, 4, dtype=torch.float32, device=dev)
+    L.check(lib.loft_det_gather_boxes(L.ptr(bboxes), box_cols, C, L.ptr(sorted_flat), L.ptr(seg_off), S, cap, L.ptr(boxes_sorted),
+                                      L.stream()), 'loft_det_gather_boxes')
+    # classes as the "levels": shift = class * (img_max + 1), batched_nms's, in the same fp32 operations
+    keep = nms_segmented(boxes_sorted, seg_off[:S + 1], cfg['iou_threshold'], max_segment=max(max(rows), 1),
+                         predicate=cfg.get('predicate', 'device'), img_max=img_max, levels=C)
+    L.check(lib.loft_det_scatter_keep(L.ptr(keep), L.ptr(sorted_flat), L.ptr(seg_off), S, cap, L.ptr(flag), L.stream()),
+            'loft_det_scatter_keep')
+    # per image, over the DENSE scores: the first max_per_img of the stable descending order = score descending across classes, ties
+    # by ascending flat index -- what `dets[:max_num]` of the per-image path cuts
+    longest = max(rows) * C
+    if longest > TOPK_MAX_SEGMENT:      # the two-stage form takes no key mask: the masked scores as keys
+        top_keys, top_vals = segmented_topk_desc(torch.where(flag.bool(), score_flat, -1.0), img_off, max_per_img, max_segment=longest,
+                                                 seg_lengths=[n * C for n in rows])
+    else:
+        top_keys, top_vals = segmented_topk_desc(score_flat, img_off, max_per_img, max_segment=longest, key_mask=flag)
+    dets = torch.empty(B, max_per_img, 5, dtype=torch.float32, device=dev)
+    labels = torch.empty(B, max_per_img, dtype=torch.int64, device=dev)
+    counts = torch.empty(B, dtype=torch.int64, device=dev)
+    rois = torch.empty(B * max_per_img, 5, dtype=torch.float32, device=dev)
+    L.check(lib.loft_det_finalize(L.ptr(top_keys), L.ptr(top_vals), L.ptr(flag), L.ptr(bboxes), box_cols, L.ptr(roi_off_d), B, C,
+                                  max_per_img, L.ptr(dets), L.ptr(labels), L.ptr(counts), L.ptr(rois), L.stream()), 'loft_det_finalize')
+    return dets, labels, counts, rois
+
+
 def mask_paste(logits, boxes, img_h, img_w, thr=0.5):
     """logits fp32 [N,S,S], boxes [N,4] -> uint8 [N,img_h,img_w]."""
     lib = L.load()

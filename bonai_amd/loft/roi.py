@@ -868,6 +868,60 @@ class LoftRoIHead(nn.Module):
         return det_bboxes, det_labels, sel.float(), offsets
 
     @torch.no_grad()
+    def batch_test_device(self, x, proposals, img_metas):
+        """simple_test_device for the B images of a batch (x: their features; proposals: simple_test_rpn's (props [B,P,5], counts
+        [B])) -> (det_bboxes [N,5], det_labels [N], class-selected mask logits [N,S,S], decoded offsets [N,2], det_counts int64 [B]
+        on the host): image-major, inside an image the order simple_test_device gives.  Every head runs ONCE -- the bbox head over
+        the RoIs of all images (padded proposal rows dropped), the mask and offset heads over all detections -- and the selection
+        between them is kernels.multiclass_nms_batched: the host reads the proposal counts and the detection counts, nothing else.
+        simple_test_device's refusals, and images of one img_shape; the NMS must be type='nms' (soft-NMS is sequential per image)."""
+        cfg = self.test_cfg
+        if cfg.get('paste_min_score') is not None:
+            raise ValueError('test_cfg.rcnn.paste_min_score filters simple_test\'s results; batch_test_device returns every detection')
+        if not self.with_mask:
+            raise NotImplementedError('batch_test_device returns mask logits: the model has no mask head')
+        if isinstance(proposals, list):
+            raise NotImplementedError('batch_test_device takes RPNHead.simple_test_rpn\'s (proposals [B,P,5], counts [B])')
+        props, counts = proposals
+        B = int(props.shape[0])
+        if len(img_metas) != B or x[0].shape[0] != B:
+            raise ValueError(f'batch_test_device: {B} images of proposals, {len(img_metas)} metas, features of {x[0].shape[0]}')
+        img_shape = img_metas[0]['img_shape']
+        for meta in img_metas:
+            if (np.asarray(meta['scale_factor'], dtype=np.float32) != 1).any():
+                raise NotImplementedError('batch_test_device: scale_factor != 1; the device path takes fixed-size tiles')
+            if tuple(meta['img_shape'][:2]) != tuple(img_shape[:2]):
+                raise NotImplementedError('batch_test_device: images of different img_shape in one batch')
+        P = int(props.shape[1])
+        cnt = [int(n) for n in counts.tolist()]
+        off = [0]
+        for n in cnt:
+            off.append(off[-1] + n)
+        none = (props.new_zeros((0, 5)), props.new_zeros((0,), dtype=torch.long), props.new_zeros((0, 0, 0)), props.new_zeros((0, 2)),
+                np.zeros(B, np.int64))
+        if off[-1] == 0:
+            return none
+        # the RoIs of all images: (image, box) of the rows below each image's count
+        live = K.h2d(np.concatenate([np.arange(b * P, b * P + n) for b, n in enumerate(cnt)]), torch.int64, props.device)
+        idx = torch.arange(B, device=props.device, dtype=props.dtype)[:, None, None].expand(B, P, 1)
+        rois = torch.cat([idx, props[:, :, :4]], 2).view(B * P, 5)[live]
+        cls_score, bbox_pred = self.bbox_head(self.bbox_roi_extractor(x[:self.bbox_roi_extractor.num_inputs], rois))
+        scores = torch.softmax(cls_score, dim=1)
+        rr = rois[:, 1:].repeat_interleave(bbox_pred.shape[1] // 4, dim=0)
+        bboxes = self.bbox_head.bbox_coder.decode(rr, bbox_pred.reshape(-1, 4), max_shape=img_shape).view(rois.shape[0], -1)
+        dets, labels, det_counts, det_rois = K.multiclass_nms_batched(bboxes, scores, off, cfg.score_thr, cfg.nms, cfg.max_per_img)
+        det_counts = det_counts.cpu().numpy()
+        N = int(det_counts.sum())
+        if N == 0:                                  # no head runs: the logits' S is not known, they are [0,0,0]
+            return none
+        det_bboxes = torch.cat([dets[b, :int(n)] for b, n in enumerate(det_counts)])
+        det_labels = torch.cat([labels[b, :int(n)] for b, n in enumerate(det_counts)])
+        det_rois = det_rois[:N]
+        sel = self._mask_logits(x, det_rois, det_labels)
+        offsets = self.offset_head.get_offsets_device(self._offset_forward(x, det_rois), det_bboxes[:, :4].contiguous()).float()
+        return det_bboxes, det_labels, sel.float(), offsets, det_counts
+
+    @torch.no_grad()
     def aug_test(self, x, proposals, img_metas, elems, rescale=False):
         """Test-time augmentation over the V views of one tile (x: their features as a batch of V; proposals [n,5] in the original
         frame, from RPNHead.aug_test_rpn; elems: the views' D4 elements) -> simple_test's tuple.  Boxes, scores and masks follow

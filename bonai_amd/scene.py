@@ -82,7 +82,9 @@ class SceneDetector:
     test-time augmentation (the tiles' views would have to be merged before the scene's tiles are: not built)."""
 
     def __init__(self, model, tile=None, overlap=256, merge_thr=0.5, border=2, footprints=False, cfg=None,
-                 mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375), to_rgb=True):
+                 mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375), to_rgb=True, batch=1):
+        if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or not 1 <= batch <= PREP_CHUNK:
+            raise ValueError(f'batch must be an integer in 1 .. {PREP_CHUNK} (the tiles prepared per launch), got {batch!r}')
         tcfg = ((cfg.get('data') or {}).get('test') if cfg is not None else None) or {}
         if tile is None:
             scale = tcfg.get('img_scale', (1024, 1024))
@@ -109,13 +111,17 @@ class SceneDetector:
             raise ValueError('test_cfg.rcnn.paste_min_score is set: whole-scene inference merges every detection above score_thr')
         if not roi.with_mask:
             raise ValueError('whole-scene inference merges detections on their masks: the model has no mask head')
+        nms_type = dict(rcnn.get('nms') or {}).get('type', 'nms')
+        if batch > 1 and nms_type != 'nms':
+            raise ValueError(f"test_cfg.rcnn.nms type '{nms_type}' is sequential per image: tiles go through the model in batches "
+                             "only with type='nms'; use batch=1")
         if not 0 <= float(merge_thr) or int(border) < 0:
             raise ValueError(f'merge_thr >= 0 and border >= 0 needed, got {merge_thr} and {border}')
         if cfg is not None and cfg.get('img_norm_cfg'):
             nc = cfg.img_norm_cfg
             mean, std, to_rgb = tuple(nc['mean']), tuple(nc['std']), bool(nc.get('to_rgb', True))
         self.model, self.overlap, self.merge_thr, self.border = model, int(overlap), float(merge_thr), int(border)
-        self.footprints = bool(footprints)
+        self.footprints, self.batch = bool(footprints), int(batch)
         self.mean, self.std, self.to_rgb = tuple(float(v) for v in mean), tuple(float(v) for v in std), bool(to_rgb)
 
     # ------------------------------------------------------------------ tiles
@@ -127,7 +133,9 @@ class SceneDetector:
                                                            to_rgb=self.to_rgb))
 
     def tile_detections(self, scene):
-        """scene: uint8 [H,W,3] device tensor -> (origins int32 [T,2] numpy, per tile simple_test_device's 4-tuple)."""
+        """scene: uint8 [H,W,3] device tensor -> (origins int32 [T,2] numpy, per tile simple_test_device's 4-tuple).  batch = 1: every
+        tile through the model alone; batch > 1: groups of up to ``batch`` tiles through extract_feat, simple_test_rpn and
+        LoftRoIHead.batch_test_device (the last group may be short), cut back into the same per-tile tuples."""
         import torch
         from . import kernels as K
         H, W = int(scene.shape[0]), int(scene.shape[1])
@@ -137,11 +145,22 @@ class SceneDetector:
         with torch.no_grad():
             for c0 in range(0, len(origins), PREP_CHUNK):
                 imgs = K.scene_tile_prep(scene, table[c0:c0 + PREP_CHUNK].contiguous(), self.tile, not self.to_rgb, self.mean, self.std)
-                for k in range(imgs.shape[0]):
-                    metas = [self._meta(origins[c0 + k], H, W)]
-                    x = self.model.extract_feat(imgs[k:k + 1])
+                for g0 in range(0, imgs.shape[0], self.batch):
+                    metas = [self._meta(o, H, W) for o in origins[c0 + g0:c0 + g0 + self.batch]]
+                    x = self.model.extract_feat(imgs[g0:g0 + len(metas)])
                     props = self.model.rpn_head.simple_test_rpn(x, metas)
-                    dets.append(self.model.roi_head.simple_test_device(x, props, metas))
+                    if self.batch == 1:
+                        dets.append(self.model.roi_head.simple_test_device(x, props, metas))
+                        continue
+                    # tile_grid shifts the last tile of an axis inward, and a scene below the tile size is one row or column of equal
+                    # tiles: the tiles of a scene share img_shape
+                    assert all(m['img_shape'] == metas[0]['img_shape'] for m in metas), [m['img_shape'] for m in metas]
+                    d, l, m, o, n = self.model.roi_head.batch_test_device(x, props, metas)
+                    if d.shape[0] == 0:                # no head ran: every tile of the group gets the empty tuple
+                        dets.extend((d, l, m, o) for _ in metas)
+                        continue
+                    ends = np.cumsum(n).tolist()
+                    dets.extend((d[e - k:e], l[e - k:e], m[e - k:e], o[e - k:e]) for e, k in zip(ends, n.tolist()))
         return origins, dets
 
     def truncated(self, boxes, tiles, origins, H, W):

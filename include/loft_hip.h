@@ -755,6 +755,36 @@ int loft_scene_pair_counts(const float* logits, const float* boxes, const int32_
 int loft_scene_suppress(const int32_t* recs, int64_t R, const int32_t* area, const int32_t* rank, int N, double merge_thr,
                         int32_t* work, uint8_t* keep, void* stream);
 
+/* ---- multiclass NMS for the B images of a batch (bonai_amd/csrc/detect.hip) ------------------------------------------------------------
+ * mmdet/core/post_processing/bbox_nms.py:5-69 without a host decision between its steps.  scores fp32 [R, C+1] (background last),
+ * bboxes fp32 [R, box_cols], box_cols = 4 C or 4 (class-agnostic regression: one box per row for every class), roi_off DEVICE int64
+ * [B+1] (rows of image b; [0] = 0, [B] = R).  flat index = row * C + class, R * C < 2^31.
+ * loft_det_candidates: the (row, class) pairs with score > score_thr (strictly), compacted into one segment per (image, class),
+ * image-major, ascending flat index inside a segment (wave64 ballots and prefix counts: no atomic decides an order).  work: int32
+ * [2 B C] scratch.  -> seg_off int64 [B C + 2] (segment s = [seg_off[s], seg_off[s+1]); [B C] = the number of candidates, [B C + 1] =
+ * R C: one more segment that covers the unused rest of the arrays, for the sort), img_max fp32 [B] (the maximum over an image's
+ * candidates' coordinates: batched_nms's boxes.max(); NaN propagates; 0 without candidates), flag uint8 [R C] (1 = candidate),
+ * score_flat fp32 [R C] (the class scores, dense), cand_score fp32 [R C] / cand_flat int32 [R C] (score and flat index per candidate;
+ * -1 and 0 past the candidates).
+ * loft_det_gather_boxes: sorted_flat int32 [cap] (cand_flat in loft_segmented_sort_desc's order) -> boxes_sorted fp32 [cap, 4], zeros
+ * past the candidates; seg_off as above with num_segments = B C.
+ * loft_det_scatter_keep: flag[sorted_flat[i]] = keep_sorted[i] for every candidate: flag becomes "survived the NMS", per flat index.
+ * loft_det_finalize: top_keys / top_vals = loft_segmented_topk_desc(score_flat, segments roi_off * C, k = max_per_img, key mask =
+ * flag): the first entries of image b whose flag is set are its detections (score descending across classes, ties by ascending flat
+ * index; scores must exceed -1, the value a masked key counts as).  -> dets fp32 [B, max_per_img, 5] (box, score; rows past the
+ * count zero), labels int64 [B, max_per_img], counts int64 [B], rois fp32 [B max_per_img, 5] = (image, box) of the detections,
+ * image-major without gaps, zeros past their total. */
+int loft_det_candidates(const float* scores, const float* bboxes, int box_cols, const int64_t* roi_off_dev, int B, int C, int64_t R,
+                        float score_thr, int32_t* work, int64_t* seg_off, float* img_max, uint8_t* flag, float* score_flat,
+                        float* cand_score, int32_t* cand_flat, void* stream);
+int loft_det_gather_boxes(const float* bboxes, int box_cols, int C, const int32_t* sorted_flat, const int64_t* seg_off,
+                          int num_segments, int64_t cap, float* boxes_sorted, void* stream);
+int loft_det_scatter_keep(const uint8_t* keep_sorted, const int32_t* sorted_flat, const int64_t* seg_off, int num_segments, int64_t cap,
+                          uint8_t* flag, void* stream);
+int loft_det_finalize(const float* top_keys, const int32_t* top_vals, const uint8_t* keep_flat, const float* bboxes, int box_cols,
+                      const int64_t* roi_off_dev, int B, int C, int max_per_img, float* dets, int64_t* labels, int64_t* counts,
+                      float* rois, void* stream);
+
 /* ---- sparse backward of the RPN head -------------------------------------------------------------
  * The RPN losses (anchor_head.py:429-497, rpn_head.py:56-80) read the head outputs only at the sampled anchors (<= 256 per
  * image of 261 888), so its backward runs on the selected pixels: level_ptrs/H/W (HOST arrays, n_levels <= 8) describe the

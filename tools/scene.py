@@ -3,10 +3,12 @@
 (bonai_amd/scene.py; an extension -- the reference's tools/bonai/bonai_test.py delegates this step to an external package).
 
     python tools/scene.py CONFIG [CHECKPOINT] IMAGE [IMAGE ...] --out results.pkl [--tile N] [--overlap N] [--merge-thr F]
-                          [--footprints]
+                          [--footprints] [--batch N] [--hard-nms]
 
 Images are decoded with PIL as the dataset decodes its tiles.  ``--out`` pickles one result tuple per image in simple_test's
 layout for an image of the scene's size: (bbox_results, segm_results as COCO RLE, offset_results[, footprint RLE with --footprints]).
+``--batch N`` (1 .. 16) sends the tiles through the model N at a time (LoftRoIHead.batch_test_device); it needs test_cfg.rcnn.nms of
+type 'nms' -- soft-NMS is sequential per image -- and ``--hard-nms`` replaces the config's by type='nms' at the same iou_threshold.
 A first positional argument after CONFIG that ends in .pth / .pt is the checkpoint; without one the weights are the seeded
 initialisation (a smoke run).
 """
@@ -30,6 +32,9 @@ def main():
     ap.add_argument('--merge-thr', type=float, default=0.5,
                     help='two detections of different tiles are one building when their masks share more than this part of the smaller')
     ap.add_argument('--footprints', action='store_true', help='results become 4-tuples: the footprints\' RLE dicts as well')
+    ap.add_argument('--batch', type=int, default=1, help='tiles per pass through the model, 1 .. 16 (default 1: every tile alone)')
+    ap.add_argument('--hard-nms', action='store_true',
+                    help="test_cfg.rcnn.nms becomes type='nms' at the config's iou_threshold (--batch > 1 refuses soft-NMS)")
     args = ap.parse_args()
     ckpt = args.paths[0] if args.paths[0].endswith(('.pth', '.pt')) else None
     images = args.paths[1:] if ckpt else args.paths
@@ -40,6 +45,8 @@ def main():
     from bonai_amd.scene import SceneDetector, read_image
     cfg = Config.fromfile(args.config)
     torch.manual_seed(0)
+    if args.hard_nms:
+        cfg.test_cfg.rcnn.nms = dict(type='nms', iou_threshold=cfg.test_cfg.rcnn.nms.get('iou_threshold', 0.5))
     if cfg.get('fp16'):
         from bonai_amd import lib as L
         L.set_act16(torch.float16)
@@ -48,7 +55,8 @@ def main():
         from bonai_amd.checkpoint import load_checkpoint
         load_checkpoint(model, ckpt, strict=True)
     model = model.cuda().eval()
-    det = SceneDetector(model, tile=args.tile, overlap=args.overlap, merge_thr=args.merge_thr, footprints=args.footprints, cfg=cfg)
+    det = SceneDetector(model, tile=args.tile, overlap=args.overlap, merge_thr=args.merge_thr, footprints=args.footprints, cfg=cfg,
+                        batch=args.batch)
     results = []
     for path in images:
         t0 = time.time()
