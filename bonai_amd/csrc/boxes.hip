@@ -942,7 +942,10 @@ __global__ __launch_bounds__(1024) void random_sample_kernel(const uint8_t* __re
                 m += tot;
             }
             __syncthreads();
-            pooled = m >= k && m <= SAMPLE_POOL;      // (else: the full passes below; probability ~1e-9 for the 8k cut)
+            // else the full passes below.  m is binomial with mean 8k: m > SAMPLE_POOL is the rule for k above ~520 (a sampler
+            // with num >= 1024 over more than 16k candidates), not an accident; the RPN's k <= 256 keeps m near 2000.  m < k has
+            // probability e^-8 at k = 1 and falls fast with k.
+            pooled = m >= k && m <= SAMPLE_POOL;
         }
         if (pooled) {
             unsigned prefix = 0u;
