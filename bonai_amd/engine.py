@@ -14,12 +14,14 @@ bucket_cap_mb, what the reference's wrapper runs with).  xGMI gives 7 links x ~1
 all-reduce over 8 GPUs moves 2 * 7/8 * 25 MiB per link, ~0.3 ms -- bandwidth- rather than latency-bound, and the
 first bucket (FOA + part of the mask head) is on the wire while the mask / bbox branches are still in backward.
 """
+import contextlib
 import os
 
 import torch
 import torch.distributed as dist
 
 from . import kernels as K
+from . import nn as F2
 from .debug import DBG
 from .loss_scale import parse_loss_scale
 
@@ -315,7 +317,7 @@ class Trainer:
         # then on (bonai_amd/graphs.py); fixed-size batches only.  Capture failures fall back to eager launches, loudly.
         self.graph_features = bool(graph_features)
         self._fgraphs = None
-        self._unpack_stream = None
+        self._unpack_stream = self._wgrad_stream = None
         self._steps_run = 0          # steps THIS trainer has run (a resumed trainer starts at iter > 0 with an empty prepack registry)
         self.lr, self.mu, self.wd, self.max_norm = lr, momentum, weight_decay, (0.0 if max_norm is None else max_norm)
         self.optim = None
@@ -332,6 +334,9 @@ class Trainer:
         self.scaler = parsed if mode == 'dynamic' else None
         self.arena = FlatArena(model)
         self.reducer = BucketedAllReduce(self.arena, bucket_bytes)
+        # the unpack queue's knobs, read ONCE.  multi-GPU: smaller bursts, so the gradient buckets are ready (and reduced) earlier
+        self._unpack_limit = int(os.environ.get('LOFT_UNPACK_LIMIT', '0')) or (24 if self.reducer.enabled else 48)
+        self._unpack_note = self.reducer.note_queued if (self.reducer.enabled and os.environ.get('LOFT_NO_NOTE_FLUSH') != '1') else None
         self.world = dist.get_world_size() if self.reducer.enabled else 1
         self.gnorm_sq = torch.zeros(1, dtype=torch.float32, device=self.arena.data.device)
         self.scale_state = self._scale = None
@@ -509,76 +514,78 @@ class Trainer:
         if self.scaler is not None and sd.get('loss_scaler') is not None:      # (absent in a reference SGD state: keep the scale)
             self.scale_state.copy_(K.loss_scale_state_pack(**sd['loss_scaler']))
 
+    @contextlib.contextmanager
+    def _step_scope(self):
+        """Forward AND backward (whose data-gradient launches read the weight planes too); pair fusion's hand-over empty at both ends."""
+        on = self.arena.data.is_cuda
+        planes = dict(WEIGHT_PLANES=self.prepack.wplanes) if on and not DBG.no_prepack else {}
+        F2.PAIR_G.clear()
+        try:
+            with F2.installed(JOIN={} if on and not DBG.no_grad_join else None, HUB=None, **planes):
+                yield
+        finally:
+            F2.PAIR_G.clear()
+
+    @contextlib.contextmanager
+    def _forward_scope(self, data):
+        """The forward alone: nn._k8 and detector.forward_train rely on PREPACK and HUB_ENABLED being gone during backward."""
+        on = self.arena.data.is_cuda
+        prepack = dict(PREPACK=self.prepack) if on and not DBG.no_prepack else {}
+        try:
+            with F2.installed(HUB_ENABLED=on and not DBG.no_feat_hub, **prepack):
+                if prepack:
+                    self.prepack.run(self.iter)               # every trainable conv's BN fold + operand packing: one launch
+                if self.graph_features and on and K.PROFILE is None and F2.PREPACK is not None and hasattr(self.model, 'extract_feat'):
+                    self._graph_step_setup(data['img'])
+                yield
+        finally:
+            if self.graph_features:
+                self.model.feat_provider = None
+
+    @contextlib.contextmanager
+    def _backward_scope(self):
+        """The backward alone.  The zero pool always meets its end, the unpack queue is always joined before it is taken away."""
+        on = self.arena.data.is_cuda
+        sink = self._sink if on and not DBG.no_grad_sink else None
+        queue = ustream = wstream = None
+        try:
+            if on and not DBG.no_zero_pool:
+                K.zero_pool_begin(self.arena.data.device)     # one memset for all the backward's accumulation buffers
+            if sink is not None and not DBG.no_unpack_queue:
+                # (DBG.unpack_stream, round 6, measured and NOT the default: neutral on the plain step, +1.0 .. 1.3 ms with the reducer)
+                if DBG.unpack_stream and not DBG.no_side_stream:
+                    ustream = self._unpack_stream = self._unpack_stream or torch.cuda.Stream()
+                queue = K.UnpackQueue(limit=self._unpack_limit, note=self._unpack_note, stream=ustream)
+                if not DBG.no_side_stream and not DBG.no_wgrad_stream:
+                    wstream = self._wgrad_stream = self._wgrad_stream or torch.cuda.Stream()
+            with F2.installed(GRAD_SINK=sink, UNPACK_Q=queue, WGRAD_STREAM=wstream):
+                try:
+                    yield
+                finally:
+                    if queue is not None:
+                        queue.join()            # the main stream waits for the unpack stream before the norm / optimizer kernels
+        finally:
+            K.zero_pool_end()
+
     def train_step(self, data, lr=None):
-        """One full optimisation step: forward, losses, backward, gradient all-reduce, clip, SGD."""
+        """One full optimisation step: forward, losses, backward, gradient all-reduce, clip, SGD.  Everything handed to the autograd
+        layer lives in three nested scopes that put back what they found (nn.installed): none of it outlives the step, however it ends."""
         self.arena.grad.zero_()
         self.arena.rebind_grads()
         self.reducer.begin()
         for p in self.arena.params:
             p._loft_pending = 0
             p._loft_sunk = False
-        from . import nn as F2
-        prev_pp, prev_wpl = F2.PREPACK, K.WEIGHT_PLANES
-        if self.arena.data.is_cuda and not DBG.no_prepack:
-            F2.PREPACK = self.prepack
-            K.WEIGHT_PLANES = self.prepack.wplanes         # (fp32 parity mode: the weight operands' planes, made by run() below)
-            self.prepack.run(self.iter)                   # every trainable conv's BN fold + operand packing: one launch
-        prev_hub = F2.HUB_ENABLED
-        F2.HUB_ENABLED = self.arena.data.is_cuda and not DBG.no_feat_hub
-        F2.JOIN = {} if (self.arena.data.is_cuda and not DBG.no_grad_join) else None      # lives through forward AND backward
-        F2.PAIR_G.clear()                                 # (pair fusion's backward hand-over: nothing survives a step)
-        if self.graph_features and self.arena.data.is_cuda and K.PROFILE is None and F2.PREPACK is not None \
-                and hasattr(self.model, 'extract_feat'):
-            self._graph_step_setup(data['img'])
-        try:
-            out = self.model.train_step(data)
-        except BaseException:
-            F2.JOIN = None
-            K.WEIGHT_PLANES = prev_wpl
-            raise
-        finally:
-            F2.PREPACK = prev_pp
-            F2.HUB_ENABLED = prev_hub
-            if self.graph_features:
-                self.model.feat_provider = None
-        prev, F2.GRAD_SINK = F2.GRAD_SINK, (self._sink if self.arena.data.is_cuda and not DBG.no_grad_sink else None)
-        if self.arena.data.is_cuda and not DBG.no_zero_pool:
-            K.zero_pool_begin(self.arena.data.device)     # one memset for all the backward's accumulation buffers
-        if F2.GRAD_SINK is not None and not DBG.no_unpack_queue:
-            # multi-GPU: smaller bursts, so the gradient buckets become ready (and their all-reduce starts) earlier in backward
-            # (round 6, measured and NOT the default: the batched unpack launches on a stream of their own -- kernels.UnpackQueue,
-            #  DBG.unpack_stream -- joined below: neutral on the plain step, +1.0 .. 1.3 ms on the forced-reducer leg)
-            ustream = None
-            if DBG.unpack_stream and not DBG.no_side_stream:
-                if getattr(self, '_unpack_stream', None) is None:
-                    self._unpack_stream = torch.cuda.Stream()
-                ustream = self._unpack_stream
-            lim = int(os.environ.get('LOFT_UNPACK_LIMIT', '0')) or (24 if self.reducer.enabled else 48)
-            note = self.reducer.note_queued if (self.reducer.enabled and os.environ.get('LOFT_NO_NOTE_FLUSH') != '1') else None
-            F2.UNPACK_Q = K.UnpackQueue(limit=lim, note=note, stream=ustream)
-            if not DBG.no_side_stream and not DBG.no_wgrad_stream:
-                if getattr(self, '_wgrad_stream', None) is None:
-                    self._wgrad_stream = torch.cuda.Stream()
-                F2.WGRAD_STREAM = self._wgrad_stream
-        try:
-            if self.scaler is None:
-                (out['loss'] if self.loss_scale == 1.0 else out['loss'] * self.loss_scale).backward()
-            else:
-                # The scale enters ONLY here, as the backward seed: forward, samplers and NMS never see it, and no backward
-                # kernel branches on gradient values, so an overflow can only put inf / NaN into gradient VALUES.
-                (out['loss'] * self._scale).backward()
-            if F2.UNPACK_Q is not None:
-                F2.UNPACK_Q.flush()
-        finally:
-            if F2.UNPACK_Q is not None:
-                F2.UNPACK_Q.join()              # the main stream waits for the unpack stream before the norm / optimizer kernels
-            F2.UNPACK_Q = None
-            F2.WGRAD_STREAM = None
-            F2.GRAD_SINK = prev
-            F2.HUB = None
-            F2.JOIN = None
-            K.WEIGHT_PLANES = prev_wpl          # (the backward's data-gradient launches read the weight planes too)
-            K.zero_pool_end()
+        with self._step_scope():
+            with self._forward_scope(data):
+                out = self.model.train_step(data)
+            with self._backward_scope():
+                # Dynamic scaling: the scale enters ONLY here, as the backward seed: forward, samplers and NMS never see it, and no
+                # backward kernel branches on gradient values, so an overflow can only put inf / NaN into gradient VALUES.
+                scale = self._scale if self.scaler is not None else self.loss_scale
+                (out['loss'] if self.scaler is None and scale == 1.0 else out['loss'] * scale).backward()
+                if F2.UNPACK_Q is not None:
+                    F2.UNPACK_Q.flush()
         self.reducer.finish()
         self.gnorm_sq.zero_()
         K.sumsq_(self.arena.grad, self.gnorm_sq)

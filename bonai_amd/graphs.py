@@ -84,14 +84,14 @@ class FeatureGraphs:
         stream = torch.cuda.Stream()
         stream.wait_stream(torch.cuda.current_stream())
         from .loft import hrnet as H
-        prev = (F2.GRAD_SINK, F2.UNPACK_Q, F2.WGRAD_STREAM, F2.PREPACK, F2.HUB_ENABLED, H.BRANCH_STREAMS)
+        prev_branch = H.BRANCH_STREAMS
         zp, sp = K._ZeroPool, K._ScratchPool
         zp_state, sp_state = (zp.buf, zp.off, zp.need, zp.active), (sp.buf, sp.off, sp.need, sp.active)
         zero_need = max(int(zp.need), int(zp.buf.numel()) if zp.buf is not None else 0)     # >= what the section's backward asks for
         sp.active = False
         zp.active = False
         K.H2D_KEEP = self.keep
-        prev_trace, F2.PACK_TRACE = F2.PACK_TRACE, []
+        trace = []                    # every frozen-layer packing the captured section is handed (nn.PACK_TRACE)
         # forks inside the graphs: HRNet's branches and the weight-gradient launches keep their own streams (parallel branches of
         # the captured graph; every fork is joined before the capture ends: HRModule joins its branches, the final UnpackQueue
         # flush waits for every weight-gradient launch)
@@ -117,34 +117,32 @@ class FeatureGraphs:
         gc_was_on = gc.isenabled()
         gc.disable()
         try:
-            F2.PREPACK = tr.prepack
-            F2.HUB_ENABLED = False
             H.BRANCH_STREAMS = self.side[:3]
-            with torch.cuda.graph(self.g_fwd, stream=stream, capture_error_mode='relaxed'):
-                feats = m.extract_feat(self.static_img)
-            feats = tuple(feats)
-            self.static_grads = tuple(torch.zeros_like(f) for f in feats)
-            F2.GRAD_SINK = lambda p: None                        # (the reducer is told after each replay, not during capture)
-            F2.WGRAD_STREAM = self.side[3]
-            with torch.cuda.graph(self.g_bwd, pool=self.g_fwd.pool(), stream=stream, capture_error_mode='relaxed'):
-                if zero_need > 0:
-                    # the section's accumulation buffers: ONE slab of the graphs' private pool, zeroed by one node per replay
-                    # (bump offsets are identical in every replay: the same launches in the same order)
-                    zp.buf = torch.empty(int(zero_need * 1.05) + 1024, dtype=torch.float32, device=dev)
-                    zp.buf.zero_()
-                    zp.off, zp.need, zp.active = 0, 0, True
-                    self.keep.append(zp.buf)
-                F2.UNPACK_Q = K.UnpackQueue(limit=48)
-                for p in params:
-                    p._loft_sunk = False
-                torch.autograd.backward(list(feats), grad_tensors=list(self.static_grads))
-                F2.UNPACK_Q.flush()
-            self.static_feats = tuple(f.detach() for f in feats)      # aliases of the static maps, cut loose from the captured graph
+            with F2.installed(PREPACK=tr.prepack, HUB_ENABLED=False, PACK_TRACE=trace):
+                with torch.cuda.graph(self.g_fwd, stream=stream, capture_error_mode='relaxed'):
+                    feats = m.extract_feat(self.static_img)
+                feats = tuple(feats)
+                self.static_grads = tuple(torch.zeros_like(f) for f in feats)
+                # (GRAD_SINK: the reducer is told after each replay, not during capture)
+                with F2.installed(GRAD_SINK=lambda p: None, WGRAD_STREAM=self.side[3]), \
+                        torch.cuda.graph(self.g_bwd, pool=self.g_fwd.pool(), stream=stream, capture_error_mode='relaxed'):
+                    if zero_need > 0:
+                        # the section's accumulation buffers: ONE slab of the graphs' private pool, zeroed by one node per replay
+                        # (bump offsets are identical in every replay: the same launches in the same order)
+                        zp.buf = torch.empty(int(zero_need * 1.05) + 1024, dtype=torch.float32, device=dev)
+                        zp.buf.zero_()
+                        zp.off, zp.need, zp.active = 0, 0, True
+                        self.keep.append(zp.buf)
+                    with F2.installed(UNPACK_Q=K.UnpackQueue(limit=48)):
+                        for p in params:
+                            p._loft_sunk = False
+                        torch.autograd.backward(list(feats), grad_tensors=list(self.static_grads))
+                        F2.UNPACK_Q.flush()
+                self.static_feats = tuple(f.detach() for f in feats)      # aliases of the static maps, cut loose from the captured graph
         finally:
-            F2.GRAD_SINK, F2.UNPACK_Q, F2.WGRAD_STREAM, F2.PREPACK, F2.HUB_ENABLED, H.BRANCH_STREAMS = prev
+            H.BRANCH_STREAMS = prev_branch
             (zp.buf, zp.off, zp.need, zp.active), (sp.buf, sp.off, sp.need, sp.active) = zp_state, sp_state
             K.H2D_KEEP = None
-            trace, F2.PACK_TRACE = F2.PACK_TRACE, prev_trace
             if gc_was_on:
                 gc.enable()
         # Addresses the graphs do not own: the frozen layers' packings live in a cache on their Parameters and the

@@ -146,6 +146,7 @@ UNPACK_Q = None    # the running Trainer's kernels.UnpackQueue: weight-gradient 
 PREPACK = None     # the running Trainer's kernels.PrepackRegistry: all trainable convs' packings in one launch per step
 # Pair fusion (loft_bneck_pair_bf16): the data gradient of block k's second conv output, computed by block k+1's backward launch
 # together with ITS data gradient; keyed by the address of the gradient tensor block k+1 returns (which the entry keeps alive).
+# The Trainer's step scope clears it on entry AND on exit: an entry whose lookup missed does not outlive the step.
 PAIR_G = {}
 
 
@@ -767,10 +768,33 @@ def deconv2x2_relu(x, w, b, input_relu=False, head=None):
 # there and returns None, and the block's backward feeds the deposit to its first data-gradient launch as the epilogue's `residual`
 # (fp32 add before the rounding).  Order-safe: a consumer that finds no open entry (the block already ran, or never registered)
 # returns its gradient to autograd as before.
-JOIN = None            # {data_ptr of a block input: None (open) | deposited gradient} for the step being built / differentiated
+JOIN = None            # {data_ptr of a block input: None (open) | deposited gradient}: the Trainer's step scope (forward AND backward)
 
-HUB_ENABLED = False    # set by the Trainer for the duration of a train_step
-HUB = None             # {feature data_ptr: shared gradient map | None} of the step being differentiated
+HUB_ENABLED = False    # True in the Trainer's forward scope only: gone again during backward
+HUB = None             # {feature data_ptr: shared gradient map | None}: made by feat_hub() in the forward, None again after the step
+
+
+# ---- who sets the hand-over globals above (and kernels.WEIGHT_PLANES): installed(), and nobody else ------------------------------
+_HANDOVER = ('PREPACK', 'HUB_ENABLED', 'HUB', 'JOIN', 'GRAD_SINK', 'UNPACK_Q', 'WGRAD_STREAM', 'PACK_TRACE', 'WEIGHT_PLANES')
+
+
+@contextlib.contextmanager
+def installed(**values):
+    """Set the named hand-over globals for the duration of a ``with`` block and put back what they held BEFORE (not None: the
+    scopes nest -- FeatureGraphs.capture runs inside a Trainer step), in reverse order, however the block ends.  Any name outside
+    _HANDOVER raises before anything is changed.  WEIGHT_PLANES lives in bonai_amd.kernels, the rest in this module."""
+    unknown = sorted(set(values) - set(_HANDOVER))
+    if unknown:
+        raise TypeError(f'installed(): not a hand-over global: {unknown}')
+    prev = [(vars(K) if n == 'WEIGHT_PLANES' else globals(), n) for n in values]
+    prev = [(ns, n, ns[n]) for ns, n in prev]
+    try:
+        for (ns, n, _), v in zip(prev, values.values()):
+            ns[n] = v
+        yield
+    finally:
+        for ns, n, old in reversed(prev):
+            ns[n] = old
 
 
 class FeatFork(tuple):

@@ -9,6 +9,8 @@ What a pass between two ``Trainer.train_step`` calls has to respect, and how:
     trainer step (nn.PREPACK is None there).  Nothing has to be invalidated (tests/test_validate_gpu.py pins it).
   * training state: the pass draws no random number (the RandomSampler counter is checked), does not touch the trainer, and
     leaves the process-global hand-over tables (nn.PREPACK, kernels.WEIGHT_PLANES, nn.JOIN, nn.PAIR_G) as it found them.
+    Between two steps they are all unset / empty: only nn.installed() sets them, inside the scopes of Trainer.train_step, which
+    put back what they found however the step ends (a raise included) and clear nn.PAIR_G on the way out.
   * it runs uncaptured; tools/train.py refuses --graph together with validation.
 """
 import numpy as np

@@ -520,3 +520,118 @@ def test_gradient_join_is_order_safe_and_matches_the_autograd_sum(lateral_first)
     assert (gx1 - gx0).norm().item() <= 6e-3 * gx0.norm().item()      # one bf16 rounding less on the joined path
     for a, b in zip(pg1, pg0):
         assert (a - b).norm().item() <= 1e-2 * b.norm().item() + 1e-12
+
+
+# ---- nothing of a step's hand-over to the autograd layer outlives the step, however the step ends (Trainer's three scopes) --------
+
+def _handover(m):
+    """Every global nn.installed() knows, pair fusion's table, the zero pool's state and the model's replay provider."""
+    from bonai_amd import kernels as K
+    from bonai_amd import nn as F2
+    return ([(n, getattr(K if n == 'WEIGHT_PLANES' else F2, n)) for n in F2._HANDOVER], sorted(F2.PAIR_G), K._ZeroPool.active,
+            m.feat_provider)
+
+
+def _step_raises_and_leaves_nothing(tr, m, data, match):
+    before = _handover(m)
+    with pytest.raises(RuntimeError, match=match):
+        tr.train_step(data, lr=0.0)
+    assert _handover(m) == before, (_handover(m), before)
+
+
+def _next_step_is_finite(tr, data):
+    import math
+    loss = tr.train_step(data, lr=0.0)['log_vars']['loss']
+    torch.cuda.synchronize()
+    assert math.isfinite(loss), loss
+
+
+class _RaisingBackward(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, one):
+        return one.view_as(one)
+
+    @staticmethod
+    def backward(ctx, g):
+        raise RuntimeError('backward raised on the host')
+
+
+@pytest.mark.parametrize('where', ['forward', 'backward', 'between'])
+def test_a_raising_step_leaves_no_handover_installed(where, first_k, monkeypatch):
+    """A Python exception out of the forward (after the model ran: join, hub, planes and prepack registry were all in use), out of
+    the backward (an autograd node of the loss raises) or out of the set-up between the two (the unpack queue's constructor)
+    leaves every hand-over global, nn.PAIR_G, the zero pool and model.feat_provider as they were before the step, and the same
+    trainer then runs a whole step."""
+    from bonai_amd import kernels as K
+    from bonai_amd.engine import Trainer
+    from bonai_amd.synth import make_batch
+    data = make_batch(2, 256, 8, device='cuda')
+    m = _synth_model()
+    tr = Trainer(m, lr=0.0, momentum=0.0, weight_decay=0.0)
+    forward = m.train_step
+
+    def raising_forward(d):
+        out = forward(d)
+        if where == 'forward':
+            raise RuntimeError('forward raised on the host')
+        out['loss'] = out['loss'] * _RaisingBackward.apply(torch.ones((), device='cuda', requires_grad=True))
+        return out
+
+    def raising_queue(*a, **kw):
+        raise RuntimeError('queue raised on the host')
+    with monkeypatch.context() as mp:
+        if where == 'between':
+            mp.setattr(K, 'UnpackQueue', raising_queue)
+        else:
+            mp.setattr(m, 'train_step', raising_forward)
+        _step_raises_and_leaves_nothing(tr, m, data, ('queue' if where == 'between' else where) + ' raised on the host')
+    m.__dict__.pop('train_step', None)                    # (the class's own method again, not a bound copy on the instance)
+    _next_step_is_finite(tr, data)
+
+
+def test_a_raising_graph_setup_leaves_no_handover_installed(first_k, monkeypatch):
+    """graph_features=True: _graph_step_setup runs with PREPACK, WEIGHT_PLANES, HUB_ENABLED and JOIN installed.  A raise there
+    (FeatureGraphs.validate, before a replay) leaves none of them behind -- split_planes() outside a step must not be served the
+    registry's planes -- and the trainer's next step replays the graphs it still holds."""
+    from bonai_amd.engine import Trainer
+    from bonai_amd.graphs import FeatureGraphs
+    from bonai_amd.synth import make_batch
+    data = make_batch(2, 256, 8, device='cuda')
+    m = _synth_model()
+    tr = Trainer(m, lr=0.0, momentum=0.0, weight_decay=0.0, graph_features=True)
+    for _ in range(3):
+        tr.train_step(data, lr=0.0)
+    assert tr._fgraphs.ready and tr._fgraphs.failed is None, tr._fgraphs.failed
+
+    def raising_validate(self):
+        raise RuntimeError('validate raised on the host')
+    with monkeypatch.context() as mp:
+        mp.setattr(FeatureGraphs, 'validate', raising_validate)
+        _step_raises_and_leaves_nothing(tr, m, data, 'validate raised on the host')
+    _next_step_is_finite(tr, data)
+    assert tr._fgraphs.ready
+
+
+def test_a_step_with_pair_fusion_leaves_pair_g_empty(first_k, monkeypatch):
+    """Pair fusion hands a gradient map pair from one block's backward to the previous block's through nn.PAIR_G; the entry of the
+    last pair of a step is only dropped by the next pair launch.  The step clears the table when it ends, so the two maps do not
+    stay alive until the next step."""
+    from bonai_amd import nn as F2
+    from bonai_amd.engine import Trainer
+    from bonai_amd.synth import make_batch
+
+    class Spy(dict):
+        stored = 0
+
+        def __setitem__(self, k, v):
+            Spy.stored += 1
+            super().__setitem__(k, v)
+    monkeypatch.setattr(F2, 'PAIR_G', Spy())
+    data = make_batch(2, 256, 8, device='cuda')
+    m = _synth_model()
+    tr = Trainer(m, lr=0.0, momentum=0.0, weight_decay=0.0)
+    before = _handover(m)
+    _next_step_is_finite(tr, data)
+    assert Spy.stored > 0, 'no pair hand-over happened: the step did not use pair fusion'
+    assert len(F2.PAIR_G) == 0
+    assert _handover(m) == before
