@@ -17,6 +17,7 @@ from torch import nn
 
 from .. import kernels as K
 from .. import nn as F2
+from .. import streams
 from ..debug import DBG
 from .backbone import Bottleneck, ConvW, FrozenStatBN
 from .builder import BACKBONES, NECKS
@@ -134,21 +135,17 @@ class HRModule(nn.Module):
         with BRANCH_STREAMS set (hipGraph capture: bonai_amd/graphs.py; tests) branch i > 0 runs on its own HIP stream, forked
         from and joined to the calling stream -- in a captured graph that makes them parallel branches, and autograd replays the
         backward on the same streams."""
-        streams = BRANCH_STREAMS
-        if not streams or not x[0].is_cuda or len(streams) < self.num_branches - 1:
+        sides = BRANCH_STREAMS
+        if not sides or not x[0].is_cuda or len(sides) < self.num_branches - 1:
             return [self.branches[i](x[i]) for i in range(self.num_branches)]
-        main = torch.cuda.current_stream()
         ys = [None] * self.num_branches
         for i in range(1, self.num_branches):
-            s = streams[i - 1]
-            s.wait_stream(main)
-            x[i].record_stream(s)
-            with torch.cuda.stream(s):
+            streams.fork(sides[i - 1], x[i])
+            with streams.on(sides[i - 1]):
                 ys[i] = self.branches[i](x[i])
         ys[0] = self.branches[0](x[0])
         for i in range(1, self.num_branches):
-            main.wait_stream(streams[i - 1])
-            ys[i].record_stream(main)
+            streams.join(sides[i - 1], ys[i])
         return ys
 
     def forward(self, x):

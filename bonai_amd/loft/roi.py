@@ -20,6 +20,7 @@ from .. import kernels as K
 from .. import rle
 from ..debug import DBG
 from .. import nn as F2
+from .. import streams
 from .backbone import ConvW
 from .builder import (HEADS, ROI_EXTRACTORS, build_assigner, build_bbox_coder, build_head, build_loss,
                       build_roi_extractor, build_sampler)
@@ -552,156 +553,156 @@ class LoftRoIHead(nn.Module):
         self.offset_head.init_weights()
 
     # ---------------------------------------------------------------- training
-    def forward_train(self, x, img_metas, proposal_list, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_masks=None,
-                      gt_offsets=None):
-        """proposal_list: (proposals [B,P,5], counts [B]) from RPNHead, or the reference's list of (n_i,5) tensors."""
-        dev = x[0].device
-        B = len(img_metas)
-        if isinstance(proposal_list, (list,)):
-            P = max(1, max(int(p.shape[0]) for p in proposal_list))
-            props = torch.zeros(B, P, 5, device=dev)
-            for i, p in enumerate(proposal_list):
-                props[i, :p.shape[0], :p.shape[1]] = p
-            nprop = K.h2d([int(p.shape[0]) for p in proposal_list], torch.int64, dev)
-        else:
-            props, nprop = proposal_list
+    def _padded_proposals(self, proposal_list, B, dev):
+        """-> (proposals [B,P,5], counts [B]): RPNHead's pair as it is, the reference's list padded to it.  Main stream."""
+        if not isinstance(proposal_list, list):
+            return proposal_list
+        P = max(1, max(int(p.shape[0]) for p in proposal_list))
+        props = torch.zeros(B, P, 5, device=dev)
+        for i, p in enumerate(proposal_list):
+            props[i, :p.shape[0], :p.shape[1]] = p
+        return props, K.h2d([int(p.shape[0]) for p in proposal_list], torch.int64, dev)
+
+    @torch.no_grad()
+    def _assign_and_sample(self, props, nprop, gt_bboxes, gt_labels, dev):
+        """MaxIoUAssigner + RandomSampler for the batch -> what both target stages read, in roi_sample_targets' argument order:
+        (cand [B,N,4], gt_inds [B,N], gts [B,Kmax,4], lab_pad [B,Kmax], pos_idx, pos_valid, neg_idx, neg_valid).  Main stream."""
+        gts, ngt = pad_gts(gt_bboxes, dev)
+        gt_inds, _ = self.bbox_assigner.assign_batched(props[..., :4].contiguous(), nprop.int(), gts, ngt)
+        cand = props[..., :4]
+        if self.bbox_sampler.add_gt_as_proposals:
+            gt_inds = torch.cat([gt_self_inds(gt_bboxes, dev), gt_inds], 1)
+            cand = torch.cat([gts, cand], 1)
+        smp = self.bbox_sampler.sample_batched(gt_inds)
+        return (cand, gt_inds, gts, pad_rows(gt_labels, dev, torch.long, gts.shape[1]), smp['pos_idx'], smp['pos_valid'],
+                smp['neg_idx'], smp['neg_valid'])
+
+    # Two formulations of the sampled lists and targets, per image [pos..., neg...] (SamplingResult.bboxes, sampling_result.py:50-53):
+    # both return the record of kernels._RoiTargets.finish().
+
+    def _targets_fused(self, xb, sampled):
+        """One launch (loft_roi_sample_targets) and the step's one host sync of the RoI head -> (record, the bbox extractor's
+        features of record['rois'] or None).  Main stream."""
+        head = self.bbox_head
         with torch.no_grad():
-            gts, ngt = pad_gts(gt_bboxes, dev)
-            Kmax = gts.shape[1]
-            gi_p, _ = self.bbox_assigner.assign_batched(props[..., :4].contiguous(), nprop.int(), gts, ngt)
-            if self.bbox_sampler.add_gt_as_proposals:
-                gi_g = gt_self_inds(gt_bboxes, dev)
-                gt_inds = torch.cat([gi_g, gi_p], 1)
-                cand = torch.cat([gts, props[..., :4]], 1)
-            else:
-                gt_inds, cand = gi_p, props[..., :4]
-            smp = self.bbox_sampler.sample_batched(gt_inds)
-            pidx, pval, nidx, nval = smp['pos_idx'], smp['pos_valid'], smp['neg_idx'], smp['neg_valid']
-            lab_pad = pad_rows(gt_labels, dev, torch.long, Kmax)
-        fused_targets = dev.type == 'cuda' and not TENSOR_TARGETS
+            pending = K.roi_sample_targets_begin(*sampled, head.num_classes, head.bbox_coder.means, head.bbox_coder.stds,
+                                                 num_expected=self.bbox_sampler.num)
+        # The bbox extractor runs on the worst-case RoI list BEFORE the host learns the counts: the GPU has ~0.3 ms of work
+        # while the host waits for them and then enqueues the branches (the read used to leave the device idle).  Every
+        # sampler slot is filled in all but degenerate batches; otherwise the result is dropped and the caller recomputes.
         spec_feats = None
-        if fused_targets:
-            # per image [pos..., neg...] (SamplingResult.bboxes, sampling_result.py:50-53), labels and bbox targets: one launch
-            with torch.no_grad():
-                pending = K.roi_sample_targets_begin(cand, gt_inds, gts, lab_pad, pidx, pval, nidx, nval,
-                                                     self.bbox_head.num_classes, self.bbox_head.bbox_coder.means,
-                                                     self.bbox_head.bbox_coder.stds, num_expected=self.bbox_sampler.num)
-            # The bbox extractor runs on the worst-case RoI list BEFORE the host learns the counts: the GPU has ~0.3 ms of work
-            # while the host waits for them and then enqueues the branches (the read used to leave the device idle).  Every
-            # sampler slot is filled in all but degenerate batches; otherwise the result is dropped and recomputed below.
-            if SPECULATIVE_BBOX_ROIALIGN and pending.rois_max.shape[0] > 0:
-                xb_ = x.branches[1] if isinstance(x, F2.FeatFork) else x
-                spec_feats = self.bbox_roi_extractor(xb_[:self.bbox_roi_extractor.num_inputs], pending.rois_max)
-            tg = pending.finish()
-            rois, labels, label_weights = tg['rois'], tg['labels'], tg['label_weights']
-            bbox_targets, bbox_weights = tg['bbox_targets'], tg['bbox_weights']
-            pos_rois, pos_b, pos_gt_i, pos_sel = tg['pos_rois'], tg['pos_b'], tg['pos_gt_i'], tg['pos_sel']
-            M = rois.shape[0]
+        if SPECULATIVE_BBOX_ROIALIGN and pending.rois_max.shape[0] > 0:
+            spec_feats = self.bbox_roi_extractor(xb[:self.bbox_roi_extractor.num_inputs], pending.rois_max)
+        tg = pending.finish()
+        if spec_feats is not None and spec_feats.shape[0] != tg['rois'].shape[0]:
+            F2.roi_align_discard(spec_feats)     # under-filled sampler: the speculative node is dropped, never differentiated
+            spec_feats = None
+        return tg, spec_feats
+
+    @torch.no_grad()
+    def _targets_tensor(self, sampled):
+        """The tensor formulation of _targets_fused (TENSOR_TARGETS, host tensors); two host syncs (nonzero).  Main stream."""
+        cand, gt_inds, gts, lab_pad, pidx, pval, nidx, nval = sampled
+        dev = cand.device
+        idx = torch.cat([pidx, nidx], 1)
+        val = torch.cat([pval, nval], 1)
+        is_pos = torch.cat([pval, torch.zeros_like(nval)], 1)
+        bidx = torch.arange(len(idx), device=dev)[:, None].expand_as(idx)
+        sel = val.reshape(-1).nonzero(as_tuple=False).flatten()
+        b_s, i_s, pos_s = bidx.reshape(-1)[sel], idx.reshape(-1)[sel], is_pos.reshape(-1)[sel]
+        boxes_s = cand[b_s, i_s]
+        rois = torch.cat([b_s[:, None].float(), boxes_s], 1)
+        assigned = (gt_inds[b_s, i_s] - 1).clamp(min=0)
+        pos_sel = pos_s.nonzero(as_tuple=False).flatten()
+        pos_rois, pos_b, pos_gt_i = rois[pos_sel], b_s[pos_sel], assigned[pos_sel]
+        pos_gt_boxes = gts[pos_b, pos_gt_i]
+        M = rois.shape[0]
+        labels = torch.full((M,), self.bbox_head.num_classes, dtype=torch.long, device=dev)
+        labels[pos_sel] = lab_pad[pos_b, pos_gt_i]
+        bbox_targets = torch.zeros(M, 4, device=dev)
+        bbox_weights = torch.zeros(M, 4, device=dev)
+        if pos_sel.numel():
+            bbox_targets[pos_sel] = self.bbox_head.bbox_coder.encode(pos_rois[:, 1:].contiguous(), pos_gt_boxes)
+            bbox_weights[pos_sel] = 1.0
+        return dict(rois=rois, labels=labels, label_weights=torch.ones(M, device=dev), bbox_targets=bbox_targets,
+                    bbox_weights=bbox_weights, pos_rois=pos_rois, pos_b=pos_b, pos_gt_i=pos_gt_i, pos_sel=pos_sel)
+
+    def _bbox_loss(self, bbox_feats, tg, from_get_targets):
+        """bbox head and its two losses.  Any stream forked behind the RoIAlign that made ``bbox_feats``."""
+        cls_score, bbox_pred = self.bbox_head(bbox_feats)
+        return self.bbox_head.loss(cls_score, bbox_pred, tg['rois'], tg['labels'], tg['label_weights'], tg['bbox_targets'],
+                                   tg['bbox_weights'], from_get_targets=from_get_targets)
+
+    def _mask_loss(self, mask_feats, tg, gt_masks):
+        """Mask head, its targets and its loss.  Any stream forked behind the RoIAlign that made ``mask_feats``."""
+        pos_rois, dev = tg['pos_rois'], mask_feats.device
+        mask_pred = self.mask_head(mask_feats)
         with torch.no_grad():
-          if not fused_targets:
-              # per image [pos..., neg...] (SamplingResult.bboxes, sampling_result.py:50-53); two host syncs (nonzero)
-              idx = torch.cat([pidx, nidx], 1)
-              val = torch.cat([pval, nval], 1)
-              is_pos = torch.cat([pval, torch.zeros_like(nval)], 1)
-              bidx = torch.arange(B, device=dev)[:, None].expand_as(idx)
-              sel = val.reshape(-1).nonzero(as_tuple=False).flatten()
-              b_s, i_s, pos_s = bidx.reshape(-1)[sel], idx.reshape(-1)[sel], is_pos.reshape(-1)[sel]
-              boxes_s = cand[b_s, i_s]
-              rois = torch.cat([b_s[:, None].float(), boxes_s], 1)
-              assigned = (gt_inds[b_s, i_s] - 1).clamp(min=0)
-              pos_sel = pos_s.nonzero(as_tuple=False).flatten()
-              pos_rois, pos_b, pos_gt_i = rois[pos_sel], b_s[pos_sel], assigned[pos_sel]
-              pos_gt_boxes = gts[pos_b, pos_gt_i]
-              M = rois.shape[0]
-              labels = torch.full((M,), self.bbox_head.num_classes, dtype=torch.long, device=dev)
-              labels[pos_sel] = lab_pad[pos_b, pos_gt_i]
-              bbox_targets = torch.zeros(M, 4, device=dev)
-              bbox_weights = torch.zeros(M, 4, device=dev)
-              if pos_sel.numel():
-                  bbox_targets[pos_sel] = self.bbox_head.bbox_coder.encode(pos_rois[:, 1:].contiguous(), pos_gt_boxes)
-                  bbox_weights[pos_sel] = 1.0
-              label_weights = torch.ones(M, device=dev)
-        self.last_stats = dict(num_rois=int(M), num_pos=int(pos_sel.numel()))
+            masks, moffs = _masks_to_device(gt_masks, dev)
+            H, W = masks[0].shape[1], masks[0].shape[2]
+            pb = pos_rois[:, 1:].clone()
+            pb[:, 0::2].clamp_(0, W)      # (strided views: list indices would cost two H2D copies and six launches)
+            pb[:, 1::2].clamp_(0, H)
+            gidx = tg['pos_gt_i'] + K.h2d(moffs[:-1], torch.int64, dev)[tg['pos_b']]
+            mask_targets = K.mask_target(masks, pb, gidx, int(self.train_cfg.mask_size))
+        return self.mask_head.loss(mask_pred, mask_targets, tg['labels'][tg['pos_sel']])
 
-        losses = dict()
-        xb = xm = xo = x
-        if isinstance(x, F2.FeatFork):       # own aliases per extractor: their backward kernels share one gradient map per level
-            xb, xm, xo = x.branches[1], x.branches[2], x.branches[3]
-        feats = xb[:self.bbox_roi_extractor.num_inputs]
-        if spec_feats is not None and spec_feats.shape[0] == rois.shape[0]:
-            bbox_feats = spec_feats
-        else:
-            if spec_feats is not None:           # under-filled sampler: the speculative node is dropped, never differentiated
-                F2.roi_align_discard(spec_feats)
-                spec_feats = None
-            bbox_feats = self.bbox_roi_extractor(feats, rois)
-
-        def bbox_branch():
-            cls_score, bbox_pred = self.bbox_head(bbox_feats)
-            return self.bbox_head.loss(cls_score, bbox_pred, rois, labels, label_weights, bbox_targets, bbox_weights,
-                                       from_get_targets=fused_targets)
-        bbox_on_side = self.with_mask and not DBG.no_bbox_side_stream   # the bbox head's 512-workgroup GEMMs ride along
-        if not bbox_on_side:
-            losses.update(bbox_branch())
-
-        side = None
-        if self.with_mask:
-            # The mask branch (4 convs + deconv + logits at 14x14 / 28x28) and the FOA branch (40 convs at 7x7) are independent
-            # chains of launches that each fill 2.6 rounds of the 256 CUs: on two HIP streams their tails fill each other's
-            # idle CUs, forward and (autograd replays each node on its forward stream) backward.  RoIAlign stays on the main
-            # stream -- its backward accumulates into the shared per-level gradient maps.
-            mask_losses = dict()
-            if dev.type == 'cuda' and torch.is_grad_enabled() and K.PROFILE is None and not DBG.no_side_stream:
-                if getattr(self, '_side_stream', None) is None:
-                    self._side_stream = torch.cuda.Stream()
-                side = self._side_stream
-                if bbox_on_side:
-                    # the bbox head forks right behind ITS RoIAlign: its two FC GEMMs and loss launches (~0.3 ms) run beside the
-                    # mask extractor's RoIAlign (0.28 ms of dependent loads that leave the matrix pipes idle) instead of after it
-                    side.wait_stream(torch.cuda.current_stream())
-                    bbox_feats.record_stream(side)
-                    with torch.cuda.stream(side):
-                        mask_losses.update(bbox_branch())
-            mask_feats = self.mask_roi_extractor(xm[:self.mask_roi_extractor.num_inputs], pos_rois)
-            if side is not None:
-                side.wait_stream(torch.cuda.current_stream())
-                mask_feats.record_stream(side)
-
-            def mask_branch():
-                mask_pred = self.mask_head(mask_feats)
-                with torch.no_grad():
-                    masks, moffs = _masks_to_device(gt_masks, dev)
-                    H, W = masks[0].shape[1], masks[0].shape[2]
-                    pb = pos_rois[:, 1:].clone()
-                    pb[:, 0::2].clamp_(0, W)      # (strided views: list indices would cost two H2D copies and six launches)
-                    pb[:, 1::2].clamp_(0, H)
-                    gidx = pos_gt_i + K.h2d(moffs[:-1], torch.int64, dev)[pos_b]
-                    mask_targets = K.mask_target(masks, pb, gidx, int(self.train_cfg.mask_size))
-                return self.mask_head.loss(mask_pred, mask_targets, labels[pos_sel])
-            if side is not None:
-                with torch.cuda.stream(side):
-                    mask_losses.update(mask_branch())
-            else:
-                if bbox_on_side:
-                    losses.update(bbox_branch())
-                losses.update(mask_branch())
-
+    def _offset_loss(self, xo, tg, gt_offsets, Kmax):
+        """Offset (FOA) extractor, head, targets and loss.  Main stream: it holds a RoIAlign."""
+        pos_rois, dev = tg['pos_rois'], tg['pos_rois'].device
         with torch.no_grad():
             off_pad = pad_rows(gt_offsets, dev, torch.float32, Kmax)
-            pos_gt_off = off_pad[pos_b, pos_gt_i]
+            pos_gt_off = off_pad[tg['pos_b'], tg['pos_gt_i']]
         offset_pred = self._offset_forward(xo, pos_rois)
         with torch.no_grad():
             offset_targets = self.offset_head.get_targets(pos_rois[:, 1:].contiguous(), pos_gt_off)
         if offset_pred.shape[0] == 0:
-            losses.update(loss_offset=offset_pred.sum() * 0)
-        else:
-            losses.update(self.offset_head.loss(offset_pred, offset_targets))
+            return dict(loss_offset=offset_pred.sum() * 0)
+        return self.offset_head.loss(offset_pred, offset_targets)
+
+    def forward_train(self, x, img_metas, proposal_list, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_masks=None,
+                      gt_offsets=None):
+        """proposal_list: (proposals [B,P,5], counts [B]) from RPNHead, or the reference's list of (n_i,5) tensors."""
+        dev = x[0].device
+        props, nprop = self._padded_proposals(proposal_list, len(img_metas), dev)
+        sampled = self._assign_and_sample(props, nprop, gt_bboxes, gt_labels, dev)
+        xb = xm = xo = x
+        if isinstance(x, F2.FeatFork):       # own aliases per extractor: their backward kernels share one gradient map per level
+            xb, xm, xo = x.branches[1], x.branches[2], x.branches[3]
+        fused_targets = dev.type == 'cuda' and not TENSOR_TARGETS
+        tg, bbox_feats = self._targets_fused(xb, sampled) if fused_targets else (self._targets_tensor(sampled), None)
+        self.last_stats = dict(num_rois=int(tg['rois'].shape[0]), num_pos=int(tg['pos_sel'].numel()))
+        if bbox_feats is None:
+            bbox_feats = self.bbox_roi_extractor(xb[:self.bbox_roi_extractor.num_inputs], tg['rois'])
+
+        # The mask branch (4 convs + deconv + logits at 14x14 / 28x28) and the FOA branch (40 convs at 7x7) are independent
+        # chains of launches that each fill 2.6 rounds of the 256 CUs: on two HIP streams their tails fill each other's
+        # idle CUs, forward and (autograd replays each node on its forward stream) backward.  RoIAlign stays on the main
+        # stream -- its backward accumulates into the shared per-level gradient maps.
+        side = streams.owned(self, '_side_stream') if self.with_mask and streams.enabled(x[0]) else None
+        losses = dict()
+        made = losses if side is None else dict()       # (what the side stream makes joins ``losses`` last)
+        bbox_late = self.with_mask and not DBG.no_bbox_side_stream   # the bbox head's 512-workgroup GEMMs ride along
+        if not bbox_late:
+            losses.update(self._bbox_loss(bbox_feats, tg, fused_targets))
+        elif side is not None:
+            # the bbox head forks right behind ITS RoIAlign: its two FC GEMMs and loss launches (~0.3 ms) run beside the
+            # mask extractor's RoIAlign (0.28 ms of dependent loads that leave the matrix pipes idle) instead of after it
+            streams.fork(side, bbox_feats)
+            with streams.on(side):
+                made.update(self._bbox_loss(bbox_feats, tg, fused_targets))
+        if self.with_mask:
+            mask_feats = self.mask_roi_extractor(xm[:self.mask_roi_extractor.num_inputs], tg['pos_rois'])
+            if side is not None:
+                streams.fork(side, mask_feats)
+            elif bbox_late:
+                losses.update(self._bbox_loss(bbox_feats, tg, fused_targets))
+            with streams.on(side):
+                made.update(self._mask_loss(mask_feats, tg, gt_masks))
+        losses.update(self._offset_loss(xo, tg, gt_offsets, sampled[2].shape[1]))
         if side is not None:
-            main = torch.cuda.current_stream()
-            main.wait_stream(side)
-            for v in mask_losses.values():
-                v.record_stream(main)
-            losses.update(mask_losses)
+            streams.join(side, *made.values())
+            losses.update(made)
         return losses
 
     # ---------------------------------------------------------------- inference

@@ -13,7 +13,6 @@ proposal semantics.  What changed underneath:
   * the losses are evaluated on the <=512 sampled anchors per image only (identical value: all other
     anchors carry weight 0 in anchor_head.py:180-245).
 """
-import contextlib
 import os
 
 import torch
@@ -22,6 +21,7 @@ from torch import nn
 from .. import kernels as K
 from ..debug import DBG
 from .. import nn as F2
+from .. import streams
 from .backbone import ConvW
 from .builder import HEADS, build_anchor_generator, build_assigner, build_bbox_coder, build_loss, build_sampler
 from .core import pad_gts
@@ -150,8 +150,8 @@ class RPNHead(nn.Module):
         (tools/probes/stage_events.py: that window was 0.80 ms).  loss_fused picks the result up if the geometry it sees is the
         one predicted here from the image size; otherwise it recomputes."""
         self._prefetched = None
-        if not (img.is_cuda and self.sparse_backward and torch.is_grad_enabled() and K.PROFILE is None and not DBG.no_side_stream
-                and not DBG.no_rpn_target_prefetch) or self.train_cfg.get('allowed_border', -1) >= 0:
+        if not (streams.enabled(img) and self.sparse_backward and not DBG.no_rpn_target_prefetch) \
+                or self.train_cfg.get('allowed_border', -1) >= 0:
             return
         dev = img.device
         sizes, (h, w) = [], (int(img.shape[2]), int(img.shape[3]))
@@ -166,14 +166,9 @@ class RPNHead(nn.Module):
         B = int(img.shape[0])
         geo = self._geometry_of(tuple(sizes), B, dev)
         gts, ngt = pad_gts(gt_bboxes, dev)              # (on the calling stream: the RoI head reads the same cached pair)
-        main = torch.cuda.current_stream()
-        if getattr(self, '_tgt_stream', None) is None:
-            self._tgt_stream = torch.cuda.Stream()
-        side = self._tgt_stream
-        side.wait_stream(main)
-        gts.record_stream(side)                         # (allocated on `main`, read on `side`: the caching allocator must not hand
-        ngt.record_stream(side)                         #  the blocks out again while the side stream still reads them -- ADVICE r4)
-        with torch.cuda.stream(side):
+        side = streams.owned(self, '_tgt_stream')
+        streams.fork(side, gts, ngt)                    # (joined by _targets' event wait, in another call: both may be freed before)
+        with streams.on(side):
             out = self._assign_and_sample(geo, B, gts, ngt, dev)
             done = torch.cuda.Event()
             done.record(side)
@@ -183,10 +178,7 @@ class RPNHead(nn.Module):
         gts, ngt = pad_gts(gt_bboxes, dev)
         pre, self._prefetched = getattr(self, '_prefetched', None), None
         if pre is not None and pre[0] is geo and pre[1] == tuple((g.data_ptr(), g._version) for g in gt_bboxes):
-            main = torch.cuda.current_stream()
-            main.wait_event(pre[3])
-            for t in pre[2]:
-                t.record_stream(main)
+            streams.join(self._tgt_stream, *pre[2], after=pre[3])
             return (gts, ngt) + pre[2]
         if pre is not None:
             # the prediction missed (another geometry or gt list than prefetch_targets saw): the side stream's work is dropped, but
@@ -199,92 +191,104 @@ class RPNHead(nn.Module):
         return (gts, ngt) + self._assign_and_sample(geo, B, gts, ngt, dev)
 
     # ---------------------------------------------------------------- loss
+    # Three gathers of what the two losses read, each on the current stream -> (logit [B,S], pred [B,P,4], tgt [B,P,4], label [B,S],
+    # weight [B,S], pos_weight like pred): S = P + Q sampled anchors per image, positives first.
+    def _sparse_outputs(self, vals, rows, slot, sparse):
+        """The gathered head outputs [B,S,5] as ONE autograd node over the sampled anchors (bonai_amd.nn._SparseRPNFn); fused was
+        computed without a graph."""
+        xs, hs = sparse
+        return F2.rpn_sparse_outputs(vals.reshape(-1, 5), rows, slot, self.num_anchors, list(xs), list(hs), self.rpn_conv.weight,
+                                     self.rpn_conv.bias, self.rpn_cls.weight, self.rpn_cls.bias, self.rpn_reg.weight,
+                                     self.rpn_reg.bias).view(vals.shape)
+
+    def _gather_kernel(self, fused, geo, sparse, gts, gt_inds, pidx, pval, nidx, nval):
+        """One launch (loft_rpn_sample_gather): level / pixel / slot of every sampled anchor, its logit + deltas straight from the
+        fused head outputs, labels, weights and the positives' regression targets; sparse backward."""
+        with torch.no_grad():
+            vals, rows, slot, tgt, label, w = K.rpn_sample_gather(list(fused), geo['lvl_off'], self.num_anchors, geo['anchors'], gts,
+                                                                  gt_inds, pidx, pval, nidx, nval, self.bbox_coder.means,
+                                                                  self.bbox_coder.stds)
+        vals = self._sparse_outputs(vals, rows, slot, sparse)
+        pred = vals[:, :pidx.shape[1], 1:5]
+        # (the positives' weights ARE pos_valid: read as one byte per row by the loss kernel, no expand / cast launches)
+        return vals[..., 0], pred, tgt, label, w, pval[..., None].expand_as(pred)
+
+    def _tensor_targets(self, geo, gts, gt_inds, pidx, pval, nval, pred):
+        """(tgt, label, weight, pos_weight) of the two tensor formulations: tgt zero where pos_valid is not set, fp32 weights."""
+        with torch.no_grad():
+            pos_anchor = geo['anchors'][pidx.reshape(-1)]
+            pos_gt_i = (torch.gather(gt_inds, 1, pidx) - 1).clamp(min=0)
+            pos_gt = torch.gather(gts, 1, pos_gt_i[..., None].expand(-1, -1, 4)).reshape(-1, 4)
+            tgt = self.bbox_coder.encode(pos_anchor, pos_gt).view(len(pidx), -1, 4)
+            tgt = torch.where(pval[..., None], tgt, torch.zeros_like(tgt))
+        label = torch.cat([pval.long(), torch.zeros_like(nval, dtype=torch.long)], 1)
+        return tgt, label, torch.cat([pval, nval], 1).float(), pval[..., None].float().expand_as(pred)
+
+    def _gather_tensor(self, fused, geo, sparse, gts, gt_inds, pidx, pval, nidx, nval):
+        """The tensor formulation of _gather_kernel (TENSOR_GATHER; host tensors): same sparse backward node."""
+        sel = torch.cat([pidx, nidx], 1)
+        A, dev = self.num_anchors, sel.device
+        with torch.no_grad():
+            cls, reg = self._flatten(fused)
+            vals = torch.cat([torch.gather(cls, 1, sel)[..., None], torch.gather(reg, 1, sel[..., None].expand(-1, -1, 4))], 2)
+            if 'lvl_off_t' not in geo:      # static geometry, uploaded once
+                geo['lvl_off_t'] = torch.tensor(geo['lvl_off'], device=dev)
+                geo['lvl_w_t'] = torch.tensor([s[1] for s in geo['sizes']], device=dev)
+            off = geo['lvl_off_t']
+            lvl = torch.bucketize(sel, off[1:], right=True)
+            local = sel - off[lvl]
+            pix, slot = local // A, local % A
+            wl = geo['lvl_w_t'][lvl]
+            valid = torch.cat([pval, nval], 1)
+            rows = torch.stack([torch.arange(len(sel), device=dev)[:, None].expand_as(sel), torch.where(valid, lvl, torch.full_like(lvl, -1)),
+                                pix // wl, pix % wl], -1).reshape(-1, 4).int().contiguous()
+        vals = self._sparse_outputs(vals, rows, slot.reshape(-1), sparse)
+        pred = vals[:, :pidx.shape[1], 1:5]
+        return (vals[..., 0], pred) + self._tensor_targets(geo, gts, gt_inds, pidx, pval, nval, pred)
+
+    def _gather_dense(self, fused, geo, sparse, gts, gt_inds, pidx, pval, nidx, nval):
+        """Plain autograd through the dense head outputs (sparse_backward off, fp32 parity, narrow inputs)."""
+        cls, reg = self._flatten(fused)
+        logit = torch.gather(cls, 1, torch.cat([pidx, nidx], 1))
+        pred = torch.gather(reg, 1, pidx[..., None].expand(-1, -1, 4))
+        return (logit, pred) + self._tensor_targets(geo, gts, gt_inds, pidx, pval, nval, pred)
+
     def loss_fused(self, fused, gt_bboxes, img_metas, gt_bboxes_ignore=None, sparse=None):
         dev = fused[0].device
         geo = self._geometry(fused, dev)
         if self.train_cfg.get('allowed_border', -1) >= 0:
             raise NotImplementedError('allowed_border >= 0 (configs/loft_foa use -1: every anchor is valid)')
-        B, N = fused[0].shape[0], geo['N']
-        gts, ngt, gt_inds, pidx, pval, nidx, nval, avg = self._targets(geo, B, gt_bboxes, dev)
-        if sparse is not None and fused[0].is_cuda and not TENSOR_GATHER:
-            # one launch: level / pixel / slot of every sampled anchor, its logit + deltas straight from the fused head outputs,
-            # labels, weights and the positives' regression targets
-            xs, hs = sparse
-            A = self.num_anchors
+        gts, ngt, gt_inds, pidx, pval, nidx, nval, avg = self._targets(geo, fused[0].shape[0], gt_bboxes, dev)
+        side = None
+        if sparse is None:
+            gather = self._gather_dense
+        elif TENSOR_GATHER or not fused[0].is_cuda:
+            gather = self._gather_tensor
+        else:
+            gather = self._gather_kernel
             # The two RPN losses get a stream of their own.  Forward this changes nothing (a dozen small launches beside the proposal
             # chain either way); autograd replays a node on its forward stream, so BACKWARD the sparse RPN gradient -- ~25 small
             # launches -- runs beside the RoI heads' backward instead of after the RoIAlign backward on the main stream
             # (nn._SparseRPNFn.backward joins the hub's stream only for the scatter into the shared maps).
-            main = torch.cuda.current_stream()
-            side = None
-            if torch.is_grad_enabled() and K.PROFILE is None and not DBG.no_side_stream and not DBG.no_rpn_loss_stream:
-                if getattr(self, '_loss_stream', None) is None:
-                    self._loss_stream = torch.cuda.Stream()
-                side = self._loss_stream
-                side.wait_stream(main)
-            with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-                with torch.no_grad():
-                    vals, rows, slot, tgt, label, w = K.rpn_sample_gather(list(fused), geo['lvl_off'], A, geo['anchors'], gts, gt_inds,
-                                                                          pidx, pval, nidx, nval, self.bbox_coder.means,
-                                                                          self.bbox_coder.stds)
-                S = vals.shape[1]
-                vals = F2.rpn_sparse_outputs(vals.reshape(-1, 5), rows, slot, A, list(xs), list(hs), self.rpn_conv.weight,
-                                             self.rpn_conv.bias, self.rpn_cls.weight, self.rpn_cls.bias, self.rpn_reg.weight,
-                                             self.rpn_reg.bias).view(B, S, 5)
-                logit = vals[..., 0]
-                pred = vals[:, :pidx.shape[1], 1:5]
-                loss_cls = self.loss_cls(logit.reshape(-1, 1), label.reshape(-1), w.reshape(-1), avg_factor=avg)
-                # (the positives' weights ARE pos_valid: read as one byte per row by the loss kernel, no expand / cast launches)
-                loss_bbox = self.loss_bbox(pred, tgt, pval[..., None].expand_as(pred), avg_factor=avg)
-            if side is not None:
-                main.wait_stream(side)
-                loss_cls.record_stream(main)
-                loss_bbox.record_stream(main)
-            return dict(loss_rpn_cls=loss_cls, loss_rpn_bbox=loss_bbox)
-        with torch.no_grad():
-            pos_anchor = geo['anchors'][pidx.reshape(-1)]
-            pos_gt_i = (torch.gather(gt_inds, 1, pidx) - 1).clamp(min=0)
-            pos_gt = torch.gather(gts, 1, pos_gt_i[..., None].expand(-1, -1, 4)).reshape(-1, 4)
-            tgt = self.bbox_coder.encode(pos_anchor, pos_gt).view(B, -1, 4)
-            tgt = torch.where(pval[..., None], tgt, torch.zeros_like(tgt))
-        sel = torch.cat([pidx, nidx], 1)
-        if sparse is None:
-            cls, reg = self._flatten(fused)
-            logit = torch.gather(cls, 1, sel)
-            pred = torch.gather(reg, 1, pidx[..., None].expand(-1, -1, 4))
-        else:       # autograd sees only the sampled anchors (bonai_amd.nn._SparseRPNFn); fused was computed without a graph
-            xs, hs = sparse
-            with torch.no_grad():
-                cls, reg = self._flatten(fused)
-                vals = torch.cat([torch.gather(cls, 1, sel)[..., None], torch.gather(reg, 1, sel[..., None].expand(-1, -1, 4))], 2)
-                A = self.num_anchors
-                if 'lvl_off_t' not in geo:      # static geometry, uploaded once
-                    geo['lvl_off_t'] = torch.tensor(geo['lvl_off'], device=dev)
-                    geo['lvl_w_t'] = torch.tensor([s[1] for s in geo['sizes']], device=dev)
-                off = geo['lvl_off_t']
-                lvl = torch.bucketize(sel, off[1:], right=True)
-                local = sel - off[lvl]
-                pix, slot = local // A, local % A
-                wl = geo['lvl_w_t'][lvl]
-                valid = torch.cat([pval, nval], 1)
-                rows = torch.stack([torch.arange(B, device=dev)[:, None].expand_as(sel), torch.where(valid, lvl, torch.full_like(lvl, -1)),
-                                    pix // wl, pix % wl], -1).reshape(-1, 4).int().contiguous()
-            S = sel.shape[1]
-            vals = F2.rpn_sparse_outputs(vals.reshape(-1, 5), rows, slot.reshape(-1), A, list(xs), list(hs), self.rpn_conv.weight,
-                                         self.rpn_conv.bias, self.rpn_cls.weight, self.rpn_cls.bias, self.rpn_reg.weight,
-                                         self.rpn_reg.bias).view(B, S, 5)
-            logit = vals[..., 0]
-            pred = vals[:, :pidx.shape[1], 1:5]
-        label = torch.cat([pval.long(), torch.zeros_like(nval, dtype=torch.long)], 1)
-        w = torch.cat([pval, nval], 1).float()
-        loss_cls = self.loss_cls(logit.reshape(-1, 1), label.reshape(-1), w.reshape(-1), avg_factor=avg)
-        loss_bbox = self.loss_bbox(pred, tgt, pval[..., None].float().expand_as(pred), avg_factor=avg)
+            if streams.enabled(fused[0]) and not DBG.no_rpn_loss_stream:
+                side = streams.owned(self, '_loss_stream')
+                streams.fork(side)
+        with streams.on(side):
+            logit, pred, tgt, label, w, pos_w = gather(fused, geo, sparse, gts, gt_inds, pidx, pval, nidx, nval)
+            loss_cls = self.loss_cls(logit.reshape(-1, 1), label.reshape(-1), w.reshape(-1), avg_factor=avg)
+            loss_bbox = self.loss_bbox(pred, tgt, pos_w, avg_factor=avg)
+        if side is not None:
+            streams.join(side, loss_cls, loss_bbox)
         return dict(loss_rpn_cls=loss_cls, loss_rpn_bbox=loss_bbox)
 
+    @staticmethod
+    def _fuse(cls_scores, bbox_preds):
+        """The reference's (cls_scores, bbox_preds) -> forward_fused's layout: per level [B,5A+1,H,W] NHWC, one zero channel."""
+        return [torch.cat([c, r, c.new_zeros(c.shape[0], 1, *c.shape[2:])], 1).contiguous(memory_format=torch.channels_last)
+                for c, r in zip(cls_scores, bbox_preds)]
+
     def loss(self, cls_scores, bbox_preds, gt_bboxes, img_metas, gt_bboxes_ignore=None):
-        fused = [torch.cat([c, r, c.new_zeros(c.shape[0], 1, *c.shape[2:])], 1).contiguous(memory_format=torch.channels_last)
-                 for c, r in zip(cls_scores, bbox_preds)]
-        return self.loss_fused(fused, gt_bboxes, img_metas, gt_bboxes_ignore)
+        return self.loss_fused(self._fuse(cls_scores, bbox_preds), gt_bboxes, img_metas, gt_bboxes_ignore)
 
     # ---------------------------------------------------------------- proposals
     @torch.no_grad()
@@ -343,9 +347,7 @@ class RPNHead(nn.Module):
 
     def get_bboxes(self, cls_scores, bbox_preds, img_metas, cfg=None, rescale=False):
         """Reference return type: list of (n_i, 5) tensors."""
-        fused = [torch.cat([c, r, c.new_zeros(c.shape[0], 1, *c.shape[2:])], 1).contiguous(memory_format=torch.channels_last)
-                 for c, r in zip(cls_scores, bbox_preds)]
-        props, counts = self.get_bboxes_fused(fused, img_metas, cfg)
+        props, counts = self.get_bboxes_fused(self._fuse(cls_scores, bbox_preds), img_metas, cfg)
         return [props[i, :int(n)] for i, n in enumerate(counts.tolist())]
 
     # ---------------------------------------------------------------- train / test entry points
@@ -353,8 +355,7 @@ class RPNHead(nn.Module):
 
     def forward_train(self, x, img_metas, gt_bboxes, gt_labels=None, gt_bboxes_ignore=None, proposal_cfg=None, **kwargs):
         if self.sparse_backward and torch.is_grad_enabled() and x[0].dtype == K.L.act16() and x[0].shape[1] % 128 == 0:
-            if (proposal_cfg is not None and x[0].is_cuda and K.PROFILE is None and not DBG.no_side_stream
-                    and not DBG.no_rpn_side_stream):
+            if proposal_cfg is not None and streams.enabled(x[0]) and not DBG.no_rpn_side_stream:
                 return self._forward_train_two_streams(x, img_metas, gt_bboxes, gt_bboxes_ignore, proposal_cfg)
             with torch.no_grad():
                 fused, hs = self.forward_fused(x, keep_hidden=True)
@@ -370,10 +371,7 @@ class RPNHead(nn.Module):
         """Target assignment + sampling + losses on the calling stream, proposal generation (score sort, decode, NMS, re-sort) on
         a second HIP stream: two chains of small launches that each keep only a few CUs busy (8 workgroups in the NMS scan and
         the sampler) and share nothing but the head's outputs.  Proposals carry no gradient, so autograd never sees the stream."""
-        main = torch.cuda.current_stream()
-        if getattr(self, '_prop_stream', None) is None:
-            self._prop_stream = torch.cuda.Stream()
-        side = self._prop_stream
+        side = streams.owned(self, '_prop_stream')
         with torch.no_grad():
             fused, hs = self.forward_fused(x, keep_hidden=True)
         # The anchor tables BOTH chains read are built here, on the calling stream, before the fork.  Round 2 let the first
@@ -383,13 +381,11 @@ class RPNHead(nn.Module):
         # test_trainer_direct_grad_sink_matches_autograd_accumulation, rep 0).  _static_ready() additionally completes every
         # cached table before it can be handed to another stream.
         self._geometry(fused, fused[0].device)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
+        streams.fork(side)
+        with streams.on(side):
             props, counts = self.get_bboxes_fused([f.detach() for f in fused], img_metas, proposal_cfg)
         losses = self.loss_fused(fused, gt_bboxes, img_metas, gt_bboxes_ignore, sparse=(x, hs))
-        main.wait_stream(side)
-        props.record_stream(main)
-        counts.record_stream(main)
+        streams.join(side, props, counts)
         return losses, (props, counts)
 
     def simple_test_rpn(self, x, img_metas):

@@ -16,6 +16,7 @@ import contextlib
 import torch
 
 from . import kernels as K
+from . import streams
 from .debug import DBG
 
 
@@ -1200,7 +1201,7 @@ class _SparseRPNFn(torch.autograd.Function):
         switch = cur is not None and hub_stream is not None and hub_stream != cur
         if switch:
             hub_stream.wait_stream(cur)
-        with (torch.cuda.stream(hub_stream) if switch else contextlib.nullcontext()):
+        with streams.on(hub_stream if switch else None):
             _hub_flush()                               # the RoI extractors' maps are complete before rows are added
             dxl, ret = [], []
             for x in xs:                               # hub-managed maps: scatter into the shared gradient map of the level
@@ -1279,11 +1280,8 @@ def _rb_param_grads(g, x, w, bn, k, stride, pad, needs):
         # Nothing on the data-gradient chain reads a weight gradient, so the launch goes to a second stream and runs beside
         # the next blocks' dgrad kernels (its split-K atomics tail and its < 256-workgroup grids leave CUs idle otherwise);
         # the unpack queue waits for it with an event (UnpackQueue.add / flush).
-        cur = torch.cuda.current_stream()
-        WGRAD_STREAM.wait_stream(cur)
-        g.record_stream(WGRAD_STREAM)
-        x.record_stream(WGRAD_STREAM)
-        with torch.cuda.stream(WGRAD_STREAM):
+        streams.fork(WGRAD_STREAM, g, x)
+        with streams.on(WGRAD_STREAM):
             dwp, db = K.conv2d_wgrad(g, x, k, k, stride, pad, with_bias=True, slots_ok=True)
             _deposit(dwp[0], db[0], w, bnt, bn.eps, slots, sinks, nsplit=_nsplit(dwp))
         return None, None, None

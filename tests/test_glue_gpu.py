@@ -545,6 +545,49 @@ def test_fused_target_and_gather_launches_match_tensor_formulations_in_the_model
         assert abs(res[0][k] - res[1][k]) <= 2e-3 * max(1.0, abs(res[1][k])), (k, res[0][k], res[1][k])
 
 
+def test_roi_target_stages_and_rpn_gathers_agree_in_the_model():
+    """The RoI head's two target stages (_targets_fused / _targets_tensor) on the same sampled inputs, and the RPN head's three
+    gathers (_gather_kernel / _gather_tensor / _gather_dense) on one set of head outputs, called directly: same model, batch and
+    'first-k' sampling as the whole-step test above.  Index, label and weight fields are equal; bbox_targets within the bound of
+    test_roi_sample_targets_matches_tensor_formulation for the same kernel (equality).  The RPN gathers have no kernel-level test
+    here: the largest difference measured on this input is 0 for tgt, logit and pred (the gathers copy; the targets share
+    box_codec.h's bbox2delta), so twice that is asserted -- equality."""
+    import os
+    from bonai_amd.config import Config
+    from bonai_amd.loft import build_detector
+    from bonai_amd.loft.core import RandomSampler
+    from bonai_amd.synth import make_batch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    RandomSampler.choice_mode = 'first'
+    cfg = Config.fromfile(os.path.join(root, 'configs', 'loft_foa', 'loft_foa_r50_fpn_2x_bonai.py'))
+    torch.manual_seed(0)
+    m = build_detector(cfg.model, train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg).cuda().train()
+    data = make_batch(2, 256, 6, device='cuda')
+    rpn, roi = m.rpn_head, m.roi_head
+    with torch.no_grad():
+        x = m.extract_feat(data['img'])
+        fused, hs = rpn.forward_fused(x, keep_hidden=True)
+        props, nprop = rpn.get_bboxes_fused(fused, data['img_metas'], m.train_cfg.get('rpn_proposal', m.test_cfg.rpn))
+        dev = x[0].device
+        sampled = roi._assign_and_sample(props, nprop, data['gt_bboxes'], data['gt_labels'], dev)
+        a, b = roi._targets_fused(x, sampled)[0], roi._targets_tensor(sampled)
+        assert a['pos_sel'].numel() > 0 and a['rois'].shape[0] > a['pos_sel'].numel()
+        for k in ('rois', 'labels', 'label_weights', 'bbox_weights', 'pos_rois', 'pos_b', 'pos_gt_i', 'pos_sel', 'bbox_targets'):
+            assert torch.equal(a[k], b[k]), k
+        geo = rpn._geometry(fused, dev)
+        gts, _, gt_inds, pidx, pval, nidx, nval, _ = rpn._targets(geo, 2, data['gt_bboxes'], dev)
+        assert bool(pval.any()) and bool(nval.any())
+        args = (gts, gt_inds, pidx, pval, nidx, nval)
+        kern = rpn._gather_kernel(fused, geo, (x, hs), *args)
+        for name, other in (('tensor', rpn._gather_tensor(fused, geo, (x, hs), *args)),
+                            ('dense', rpn._gather_dense(fused, geo, None, *args))):
+            for field, p, q in zip(('logit', 'pred', 'tgt', 'label', 'weight', 'pos_weight'), kern, other):
+                print(name, field, float((p.double() - q.double()).abs().max()))
+                assert p.shape == q.shape, (name, field)
+            for field, p, q in zip(('logit', 'pred', 'tgt', 'label', 'weight', 'pos_weight'), kern, other):
+                assert bool((p == q).all()), (name, field)      # (as values: pos_weight is bool from the kernel, fp32 otherwise)
+
+
 def test_fused_roi_backward_matches_per_extractor_passes():
     """The fused RoIAlign backward of the three extractors (nn._hub_flush -> loft_roi_align_bwd_multi) against one accumulate
     pass per extractor: same data, same sampling -> the arena gradients agree to the 16-bit rounding of the shared maps."""
