@@ -426,14 +426,17 @@ LOFT_EXPORT int loft_segmented_sort_desc(const float* keys_in, float* keys_out, 
 // State lives in a caller-provided global workspace (L2 resident for the <= few thousand boxes of this path).
 #define SNMS_THREADS 1024
 
-struct SnmsState { float* x1; float* y1; float* x2; float* y2; float* sc; float* ar; int64_t* idx; };
+template <typename I>
+struct SnmsStateT { float* x1; float* y1; float* x2; float* y2; float* sc; float* ar; I* idx; };
+using SnmsState = SnmsStateT<int64_t>;          // loft_soft_nms: indices as the caller's int64
 
-__device__ __forceinline__ void snms_swap(const SnmsState& s, int a, int b) {
+template <typename I>
+__device__ __forceinline__ void snms_swap(const SnmsStateT<I>& s, int a, int b) {
     float t;
     t = s.x1[a]; s.x1[a] = s.x1[b]; s.x1[b] = t;  t = s.y1[a]; s.y1[a] = s.y1[b]; s.y1[b] = t;
     t = s.x2[a]; s.x2[a] = s.x2[b]; s.x2[b] = t;  t = s.y2[a]; s.y2[a] = s.y2[b]; s.y2[b] = t;
     t = s.sc[a]; s.sc[a] = s.sc[b]; s.sc[b] = t;  t = s.ar[a]; s.ar[a] = s.ar[b]; s.ar[b] = t;
-    int64_t u = s.idx[a]; s.idx[a] = s.idx[b]; s.idx[b] = u;
+    I u = s.idx[a]; s.idx[a] = s.idx[b]; s.idx[b] = u;
 }
 
 // exclusive block scan of one int per thread (1024 threads = 16 waves); returns the exclusive prefix, *total = sum
@@ -726,6 +729,79 @@ LOFT_EXPORT int loft_topk_merge_runs(const float* cand_keys, const int32_t* cand
     return 0;
 }
 
+// ---- the per-slot step of the soft-NMS selection, shared by soft_nms_kernel (one call, state in a global workspace, int64 indices) and
+// soft_nms_batched_kernel (one image per workgroup, state in LDS or a workspace slab, 32-bit indices): one statement of the argmax, the
+// swap (snms_swap above), the decay and the drop, so a pair decays to the same bits in both -- gaussian's expf included.
+
+// (1) first-position argmax over [i, nb): this thread's strided part, then its wave's
+__device__ __forceinline__ void snms_argmax_wave(const float* sc, int i, int nb, float& bv, int& bp) {
+    bv = -3.0e38f;
+    bp = 0x7fffffff;
+    for (int p = i + (int)threadIdx.x; p < nb; p += SNMS_THREADS) {
+        const float v = sc[p];
+        if (v > bv) { bv = v; bp = p; }      // ascending p per thread -> first maximum kept
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int op = __shfl_xor(bp, o, 64);
+        if (ov > bv || (ov == bv && op < bp)) { bv = ov; bp = op; }
+    }
+}
+// ... and the workgroup's, over the waves' results
+__device__ __forceinline__ int snms_argmax_combine(const float* red_v, const int* red_p) {
+    float v = red_v[0]; int p = red_p[0];
+    for (int w = 1; w < SNMS_THREADS / 64; ++w)
+        if (red_v[w] > v || (red_v[w] == v && red_p[w] < p)) { v = red_v[w]; p = red_p[w]; }
+    return p;
+}
+
+// (3) the decay of box p against the selected box (ix1 .. iar); stores and returns the new score
+template <typename I>
+__device__ __forceinline__ float snms_decay(const SnmsStateT<I>& s, int p, float ix1, float iy1, float ix2, float iy2, float iar,
+                                            int method, float iou_thr, float sigma) {
+    const float xx1 = fmaxf(ix1, s.x1[p]), yy1 = fmaxf(iy1, s.y1[p]);
+    const float xx2 = fminf(ix2, s.x2[p]), yy2 = fminf(iy2, s.y2[p]);
+    const float w = fmaxf(0.f, xx2 - xx1), h = fmaxf(0.f, yy2 - yy1);
+    const float inter = w * h;
+    const float ovr = inter / (iar + s.ar[p] - inter);
+    float weight = 1.f;
+    if (method == 0) { if (ovr >= iou_thr) weight = 0.f; }
+    else if (method == 1) { if (ovr >= iou_thr) weight = 1.f - ovr; }
+    else { weight = expf(-(ovr * ovr) / sigma); }
+    const float v = s.sc[p] * weight;
+    s.sc[p] = v;
+    return v;
+}
+
+// (4) the drop, for a live tail that shrinks to [.., nb_new): holes are the dead positions < nb_new, ranked ascending; fillers the
+// survivors at positions >= nb_new, ranked descending; hole h takes filler h.  [lo, hi) is this thread's contiguous slab of the old tail
+// (slabs ascend with the thread index); fill_top[-d] is scratch for the position of the filler of descending rank d.  Every thread of
+// the workgroup calls it (block scans and a barrier inside); the caller places a barrier after it.
+template <typename I, typename Q>
+__device__ __forceinline__ void snms_drop(const SnmsStateT<I>& s, int lo, int hi, int nb_new, float min_score, Q* fill_top, int* wsum) {
+    int holes = 0, fill = 0;
+    for (int p = lo; p < hi; ++p) {
+        const bool alive = s.sc[p] >= min_score;
+        holes += (!alive && p < nb_new) ? 1 : 0;
+        fill += (alive && p >= nb_new) ? 1 : 0;
+    }
+    int tot_h, tot_f;
+    const int hole_rank0 = block_exscan(holes, &tot_h, wsum);
+    const int fill_before = block_exscan(fill, &tot_f, wsum);   // ascending rank; descending rank = tot_f-1-asc
+    int r = fill_before;
+    for (int p = lo; p < hi; ++p)
+        if (s.sc[p] >= min_score && p >= nb_new) { fill_top[-(tot_f - 1 - r)] = (Q)p; ++r; }
+    __syncthreads();
+    int hr = hole_rank0;
+    for (int p = lo; p < hi; ++p)
+        if (!(s.sc[p] >= min_score) && p < nb_new) {
+            const int src = (int)fill_top[-hr];
+            s.x1[p] = s.x1[src]; s.y1[p] = s.y1[src]; s.x2[p] = s.x2[src]; s.y2[p] = s.y2[src];
+            s.sc[p] = s.sc[src]; s.ar[p] = s.ar[src]; s.idx[p] = s.idx[src];
+            ++hr;
+        }
+}
+
 __global__ __launch_bounds__(SNMS_THREADS) void soft_nms_kernel(const float* __restrict__ boxes, const float* __restrict__ scores,
                                                                int n, float iou_thr, float sigma, float min_score, int method,
                                                                SnmsState s, float* __restrict__ dets, int64_t* __restrict__ inds,
@@ -745,23 +821,13 @@ __global__ __launch_bounds__(SNMS_THREADS) void soft_nms_kernel(const float* __r
     const int per = (n + SNMS_THREADS - 1) / SNMS_THREADS;   // contiguous slab of positions per thread (keeps scans ordered)
     for (int i = 0; i < nb; ++i) {
         // (1) first-position argmax over [i, nb)
-        float bv = -3.0e38f;
-        int bp = 0x7fffffff;
-        for (int p = i + tid; p < nb; p += SNMS_THREADS) {
-            const float v = s.sc[p];
-            if (v > bv) { bv = v; bp = p; }      // ascending p per thread -> first maximum kept
-        }
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o, 64);
-            const int op = __shfl_xor(bp, o, 64);
-            if (ov > bv || (ov == bv && op < bp)) { bv = ov; bp = op; }
-        }
+        float bv;
+        int bp;
+        snms_argmax_wave(s.sc, i, nb, bv, bp);
         if (lane == 0) { red_v[wave] = bv; red_p[wave] = bp; }
         __syncthreads();
         if (tid == 0) {
-            float v = red_v[0]; int p = red_p[0];
-            for (int w = 1; w < SNMS_THREADS / 64; ++w)
-                if (red_v[w] > v || (red_v[w] == v && red_p[w] < p)) { v = red_v[w]; p = red_p[w]; }
+            const int p = snms_argmax_combine(red_v, red_p);
             s_maxpos = p;
             // (2) swap the winner into slot i and emit it
             snms_swap(s, i, p);
@@ -774,48 +840,14 @@ __global__ __launch_bounds__(SNMS_THREADS) void soft_nms_kernel(const float* __r
         // (3) decay; (4) survivor bookkeeping on contiguous slabs [lo, hi) of the live tail (i, nb)
         const int lo = i + 1 + tid * per, hi = min(nb, lo + per);
         int surv = 0;
-        for (int p = lo; p < hi; ++p) {
-            const float xx1 = fmaxf(ix1, s.x1[p]), yy1 = fmaxf(iy1, s.y1[p]);
-            const float xx2 = fminf(ix2, s.x2[p]), yy2 = fminf(iy2, s.y2[p]);
-            const float w = fmaxf(0.f, xx2 - xx1), h = fmaxf(0.f, yy2 - yy1);
-            const float inter = w * h;
-            const float ovr = inter / (iar + s.ar[p] - inter);
-            float weight = 1.f;
-            if (method == 0) { if (ovr >= iou_thr) weight = 0.f; }
-            else if (method == 1) { if (ovr >= iou_thr) weight = 1.f - ovr; }
-            else { weight = expf(-(ovr * ovr) / sigma); }
-            const float v = s.sc[p] * weight;
-            s.sc[p] = v;
-            surv += (v >= min_score) ? 1 : 0;    // the sequential loop drops sc < min_score
-        }
+        for (int p = lo; p < hi; ++p)
+            surv += (snms_decay(s, p, ix1, iy1, ix2, iy2, iar, method, iou_thr, sigma) >= min_score) ? 1 : 0;    // the sequential loop drops sc < min_score
         int total_surv;
-        const int surv_before = block_exscan(surv, &total_surv, wsum);
+        (void)block_exscan(surv, &total_surv, wsum);
         const int nb_new = i + 1 + total_surv;
         if (nb_new < nb) {
-            // holes: dead positions < nb_new, ranked ascending; fillers: survivors at positions >= nb_new, ranked descending
-            int holes = 0, fill = 0;
-            for (int p = lo; p < hi; ++p) {
-                const bool alive = s.sc[p] >= min_score;
-                holes += (!alive && p < nb_new) ? 1 : 0;
-                fill += (alive && p >= nb_new) ? 1 : 0;
-            }
-            int tot_h, tot_f;
-            const int hole_rank0 = block_exscan(holes, &tot_h, wsum);
-            const int fill_before = block_exscan(fill, &tot_f, wsum);   // ascending rank; descending rank = tot_f-1-asc
-            // publish filler positions by descending rank into the (now free) dets tail as scratch: use inds tail
-            int r = fill_before;
-            for (int p = lo; p < hi; ++p)
-                if (s.sc[p] >= min_score && p >= nb_new) { inds[n - 1 - (tot_f - 1 - r)] = p; ++r; }  // slot n-1-d holds rank d
-            __syncthreads();
-            int hr = hole_rank0;
-            for (int p = lo; p < hi; ++p)
-                if (!(s.sc[p] >= min_score) && p < nb_new) {
-                    const int src = (int)inds[n - 1 - hr];
-                    s.x1[p] = s.x1[src]; s.y1[p] = s.y1[src]; s.x2[p] = s.x2[src]; s.y2[p] = s.y2[src];
-                    s.sc[p] = s.sc[src]; s.ar[p] = s.ar[src]; s.idx[p] = s.idx[src];
-                    ++hr;
-                }
-            (void)surv_before;
+            // filler positions by descending rank go into the (free) tail of inds as scratch: slot n-1-d holds rank d
+            snms_drop(s, lo, hi, nb_new, min_score, inds + (n - 1), wsum);
             nb = nb_new;
         }
         __syncthreads();
@@ -836,6 +868,206 @@ LOFT_EXPORT int loft_soft_nms(const float* boxes, const float* scores, int64_t n
     s.sc = (float*)w; w += 4 * n; s.ar = (float*)w;
     hipLaunchKernelGGL(soft_nms_kernel, dim3(1), dim3(SNMS_THREADS), 0, st, boxes, scores, (int)n, iou_thr, sigma, min_score,
                        method, s, dets, inds, n_out);
+    LOFT_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---------------------------------------------------------------- soft-NMS for the B images of a batch
+// LoftRoIHead.multiclass_nms with a soft_nms config (bbox_nms.py:5-69 -> batched_nms -> soft_nms -> dets[:max_num]) for every image
+// of a batch in one launch, one workgroup per image, nothing read back:
+//   candidates   scores[r, c] > score_thr, compacted in ascending flat index r * C + c (the order of `valid.nonzero()`): per 1024 flat
+//                indices a ballot per wave, the lanes below in the ballot, the waves below in the workgroup -- no atomics
+//   shift        (float)label * (max + 1.f) on the four coordinates, max = the NaN-propagating maximum over the candidates' boxes
+//                (`boxes.max()`); the same two fp32 operations as nms_mask_kernel's.  class_agnostic: no shift.
+//   selection    soft_nms_kernel's loop through the shared snms_* functions, stopped after min(selections, k) slots: the first k
+//                outputs of the sequential algorithm do not depend on later iterations, so this is dets[:max_num] bit for bit
+//   output       the UNSHIFTED box (copied from the input by index, not subtracted back) and the decayed score; zeros past the count
+// State: seven arrays per candidate (x1 y1 x2 y2 score area, 32-bit index) and one of filler positions for the drop, each `cap` 4-byte
+// words: in LDS (LDS = true; cap <= LOFT_SOFT_NMS_LDS_CAPACITY, 128 KiB at the capacity) or in image b's slab of the workspace.
+// The host picks the form from max(rows) * C.  Every barrier is reached by all threads: n, nb and the slot count are the same in
+// every thread (block sums read after a barrier), and an image without rows or candidates leaves before the first loop.
+// Barriers per slot: after the waves' argmax, after the swap, after the decay (its survivor count); the drop adds its own.
+namespace {
+__device__ __forceinline__ float snmsb_nanmax(float a, float b) { return a != a ? a : (b != b ? b : fmaxf(a, b)); }   // torch's max
+__device__ __forceinline__ float4 snmsb_box(const float* __restrict__ bboxes, int box_cols, long row, int c) {
+    return *reinterpret_cast<const float4*>(bboxes + row * box_cols + (box_cols == 4 ? 0 : 4 * c));
+}
+}  // namespace
+
+template <bool LDS>
+__global__ __launch_bounds__(SNMS_THREADS) void soft_nms_batched_kernel(const float* __restrict__ scores, const float* __restrict__ bboxes,
+                                                                       int box_cols, const int64_t* __restrict__ roi_off, int C,
+                                                                       float score_thr, int agnostic, float iou_thr, float sigma,
+                                                                       float min_score, int method, int k, int cap, float* ws,
+                                                                       float* __restrict__ dets, int64_t* __restrict__ labels,
+                                                                       int64_t* __restrict__ counts) {
+    extern __shared__ float snmsb_lds[];
+    __shared__ float red_v[SNMS_THREADS / 64];
+    __shared__ int red_p[SNMS_THREADS / 64];
+    __shared__ int wsum[SNMS_THREADS / 64];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long r0 = roi_off[b];
+    const long nflat_l = (roi_off[b + 1] - r0) * C;
+    float* base = LDS ? snmsb_lds : ws + (size_t)b * 8 * (size_t)cap;
+    SnmsStateT<int32_t> s;
+    s.x1 = base; s.y1 = base + cap; s.x2 = base + 2 * (size_t)cap; s.y2 = base + 3 * (size_t)cap;
+    s.sc = base + 4 * (size_t)cap; s.ar = base + 5 * (size_t)cap; s.idx = reinterpret_cast<int32_t*>(base + 6 * (size_t)cap);
+    int32_t* fill_top = reinterpret_cast<int32_t*>(base + 7 * (size_t)cap) + (cap - 1);
+    float* d = dets + (long)b * k * 5;
+    int64_t* lb = labels + (long)b * k;
+
+    // ---- candidates, in flat order (an image longer than the state -- the host sizes cap from the longest -- is taken as empty)
+    const int nflat = (nflat_l > 0 && nflat_l <= (long)cap) ? (int)nflat_l : 0;
+    int n = 0;
+    float m = -INFINITY;
+    for (int f0 = 0; f0 < nflat; f0 += SNMS_THREADS) {                    // uniform trip count
+        const int f = f0 + tid;
+        const int r = f / C, c = f - r * C;
+        const float sc = f < nflat ? scores[(r0 + r) * (C + 1) + c] : 0.f;
+        const bool is = f < nflat && sc > score_thr;
+        const unsigned long long bal = __ballot(is);
+        if (lane == 0) wsum[wave] = __popcll(bal);
+        __syncthreads();
+        int below = 0, chunk = 0;
+#pragma unroll
+        for (int w = 0; w < SNMS_THREADS / 64; ++w) { const int t = wsum[w]; below += w < wave ? t : 0; chunk += t; }
+        if (is) {
+            const int p = n + below + __popcll(bal & ((1ull << lane) - 1ull));
+            const float4 q = snmsb_box(bboxes, box_cols, r0 + r, c);
+            s.x1[p] = q.x; s.y1[p] = q.y; s.x2[p] = q.z; s.y2[p] = q.w; s.sc[p] = sc; s.idx[p] = f;
+            m = snmsb_nanmax(snmsb_nanmax(snmsb_nanmax(m, q.x), snmsb_nanmax(q.y, q.z)), q.w);
+        }
+        n += chunk;
+        __syncthreads();
+    }
+    if (n == 0) {                                                          // uniform: no rows, or nothing above the threshold
+        for (int r = tid; r < k; r += SNMS_THREADS) {
+            d[5 * r] = 0.f; d[5 * r + 1] = 0.f; d[5 * r + 2] = 0.f; d[5 * r + 3] = 0.f; d[5 * r + 4] = 0.f;
+            lb[r] = 0;
+        }
+        if (tid == 0) counts[b] = 0;
+        return;
+    }
+    // ---- batched_nms's shift and the areas of the shifted boxes
+    for (int o = 32; o > 0; o >>= 1) m = snmsb_nanmax(m, __shfl_xor(m, o, 64));
+    if (lane == 0) red_v[wave] = m;
+    __syncthreads();
+    m = red_v[0];
+    for (int w = 1; w < SNMS_THREADS / 64; ++w) m = snmsb_nanmax(m, red_v[w]);
+    for (int p = tid; p < n; p += SNMS_THREADS) {
+        float x1 = s.x1[p], y1 = s.y1[p], x2 = s.x2[p], y2 = s.y2[p];
+        if (!agnostic) {
+            const float shift = (float)(s.idx[p] % C) * (m + 1.f);
+            x1 += shift; y1 += shift; x2 += shift; y2 += shift;
+            s.x1[p] = x1; s.y1[p] = y1; s.x2[p] = x2; s.y2[p] = y2;
+        }
+        s.ar[p] = (x2 - x1) * (y2 - y1);
+    }
+    __syncthreads();                                                       // (also: red_v is read above, written again below)
+
+    // ---- selection
+    int nb = n, i = 0;
+    const int per = (n + SNMS_THREADS - 1) / SNMS_THREADS;
+    for (; i < nb && i < k; ++i) {
+        float bv;
+        int bp;
+        snms_argmax_wave(s.sc, i, nb, bv, bp);
+        if (lane == 0) { red_v[wave] = bv; red_p[wave] = bp; }
+        __syncthreads();
+        int p = snms_argmax_combine(red_v, red_p);                         // every thread: the same table, the same winner
+        if (p < i || p >= nb) p = i;                                       // (live scores are never NaN; never index outside the range)
+        if (tid == 0) snms_swap(s, i, p);
+        __syncthreads();
+        const float ix1 = s.x1[i], iy1 = s.y1[i], ix2 = s.x2[i], iy2 = s.y2[i], iar = s.ar[i];
+        const int lo = i + 1 + tid * per, hi = min(nb, lo + per);
+        int surv = 0;
+        for (int q = lo; q < hi; ++q)
+            surv += (snms_decay(s, q, ix1, iy1, ix2, iy2, iar, method, iou_thr, sigma) >= min_score) ? 1 : 0;
+        for (int o = 32; o > 0; o >>= 1) surv += __shfl_xor(surv, o, 64);
+        if (lane == 0) wsum[wave] = surv;
+        __syncthreads();                                                   // decayed scores and the waves' survivor counts
+        int total_surv = 0;
+#pragma unroll
+        for (int w = 0; w < SNMS_THREADS / 64; ++w) total_surv += wsum[w];
+        const int nb_new = i + 1 + total_surv;
+        if (nb_new < nb) {                                                 // uniform
+            snms_drop(s, lo, hi, nb_new, min_score, fill_top, wsum);
+            nb = nb_new;
+            __syncthreads();
+        }
+    }
+    // ---- slots [0, i) hold the selection in order (a selected slot is never touched again): boxes by index from the input
+    for (int r = tid; r < k; r += SNMS_THREADS) {
+        float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+        float sc = 0.f;
+        int c = 0;
+        if (r < i) {
+            const int f = s.idx[r];
+            const int row = f / C;
+            c = f - row * C;
+            q = snmsb_box(bboxes, box_cols, r0 + row, c);
+            sc = s.sc[r];
+        }
+        d[5 * r] = q.x; d[5 * r + 1] = q.y; d[5 * r + 2] = q.z; d[5 * r + 3] = q.w; d[5 * r + 4] = sc;
+        lb[r] = c;
+    }
+    if (tid == 0) counts[b] = i;
+}
+
+// grid: one workgroup per image.  (image, box) of every detection, compact and image-major: image b's rows start at the sum of the
+// counts before it, recomputed here from the counts the launch before wrote; zeros past the total.
+__global__ __launch_bounds__(256) void soft_nms_batched_rois_kernel(const float* __restrict__ dets, const int64_t* __restrict__ counts,
+                                                                    int B, int k, float* __restrict__ rois) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    long before = 0, all = 0;
+    for (int q = 0; q < B; ++q) {
+        const long v = counts[q];
+        all += v;
+        before += q < b ? v : 0;
+    }
+    const int mine = (int)counts[b];
+    for (int r = tid; r < mine; r += 256) {
+        const float* dd = dets + ((long)b * k + r) * 5;
+        float* ro = rois + (before + r) * 5;
+        ro[0] = (float)b; ro[1] = dd[0]; ro[2] = dd[1]; ro[3] = dd[2]; ro[4] = dd[3];
+    }
+    for (long j = all * 5 + (long)b * 256 + tid; j < (long)B * k * 5; j += (long)B * 256) rois[j] = 0.f;
+}
+
+LOFT_EXPORT int64_t loft_soft_nms_batched_workspace_bytes(int B, int64_t max_candidates) {
+    if (B < 1 || max_candidates <= LOFT_SOFT_NMS_LDS_CAPACITY) return 0;       // the LDS form
+    return (int64_t)B * 8 * 4 * max_candidates;
+}
+
+LOFT_EXPORT int loft_soft_nms_batched(const float* scores, const float* bboxes, int box_cols, const int64_t* roi_off_dev, int B, int C,
+                                      int64_t max_rows, float score_thr, int class_agnostic, float iou_thr, float sigma,
+                                      float min_score, int method, int max_per_img, void* workspace, float* dets, int64_t* labels,
+                                      int64_t* counts, float* rois, void* stream) {
+    if (B < 1 || C < 1 || max_rows < 0 || (box_cols != 4 && box_cols != 4 * C) || max_per_img < 1 || max_per_img > TOPK_MAX ||
+        method < 0 || method > 2 || max_rows * C > 0x7fffffffL)
+        return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t want = max_rows * C;
+    const int cap = (int)(want < 1 ? 1 : want);
+    if (cap <= LOFT_SOFT_NMS_LDS_CAPACITY) {
+        static bool attr_set = false;
+        if (!attr_set) {
+            const hipError_t e = hipFuncSetAttribute((const void*)soft_nms_batched_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                     8 * 4 * LOFT_SOFT_NMS_LDS_CAPACITY);
+            if (e != hipSuccess) return (int)e;
+            attr_set = true;
+        }
+        hipLaunchKernelGGL(soft_nms_batched_kernel<true>, dim3(B), dim3(SNMS_THREADS), (size_t)8 * 4 * cap, st, scores, bboxes, box_cols,
+                           roi_off_dev, C, score_thr, class_agnostic ? 1 : 0, iou_thr, sigma, min_score, method, max_per_img, cap,
+                           (float*)nullptr, dets, labels, counts);
+    } else {
+        if (workspace == nullptr) return (int)hipErrorInvalidValue;
+        hipLaunchKernelGGL(soft_nms_batched_kernel<false>, dim3(B), dim3(SNMS_THREADS), 0, st, scores, bboxes, box_cols, roi_off_dev, C,
+                           score_thr, class_agnostic ? 1 : 0, iou_thr, sigma, min_score, method, max_per_img, cap, (float*)workspace,
+                           dets, labels, counts);
+    }
+    LOFT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(soft_nms_batched_rois_kernel, dim3(B), dim3(256), 0, st, dets, counts, B, max_per_img, rois);
     LOFT_LAUNCH_CHECK();
     return 0;
 }

@@ -1863,7 +1863,8 @@ def multiclass_nms_batched(bboxes, scores, roi_off, score_thr, nms_cfg, max_per_
     cfg = dict(nms_cfg)
     typ = cfg.pop('type', 'nms')
     if typ != 'nms':
-        raise L.LoftHipError(f"multiclass_nms_batched: nms type '{typ}' is sequential per image; only type='nms' runs for a batch")
+        raise L.LoftHipError(f"multiclass_nms_batched: nms type '{typ}' is sequential per image; only type='nms' runs for a batch "
+                             "here (type='soft_nms': multiclass_soft_nms_batched)")
     if cfg.pop('class_agnostic', False):
         raise L.LoftHipError('multiclass_nms_batched: class_agnostic=True suppresses across classes; its segments are (image, class)')
     max_per_img = int(max_per_img)
@@ -1928,6 +1929,69 @@ def multiclass_nms_batched(bboxes, scores, roi_off, score_thr, nms_cfg, max_per_
     rois = torch.empty(B * max_per_img, 5, dtype=torch.float32, device=dev)
     L.check(lib.loft_det_finalize(L.ptr(top_keys), L.ptr(top_vals), L.ptr(flag), L.ptr(bboxes), box_cols, L.ptr(roi_off_d), B, C,
                                   max_per_img, L.ptr(dets), L.ptr(labels), L.ptr(counts), L.ptr(rois), L.stream()), 'loft_det_finalize')
+    return dets, labels, counts, rois
+
+
+SOFT_NMS_LDS_CAPACITY = 4096     # loft_hip.h LOFT_SOFT_NMS_LDS_CAPACITY: candidates per image whose selection state fits a workgroup's LDS
+_SOFT_NMS_METHODS = {'naive': 0, 'linear': 1, 'gaussian': 2}
+
+
+def multiclass_soft_nms_batched(bboxes, scores, roi_off, score_thr, nms_cfg, max_per_img):
+    """multiclass_nms_batched's contract -- the same inputs, outputs and input refusals -- for nms_cfg of type 'soft_nms': what
+    LoftRoIHead.multiclass_nms gives image by image (candidates in ascending row * C + class, batched_nms's shift, soft-NMS's
+    in-place max selection, the cut at max_per_img), one workgroup per image in one launch (nms.hip loft_soft_nms_batched), nothing
+    read back.  nms_cfg: iou_threshold, and optionally sigma (0.5), min_score (1e-3), method ('linear') -- kernels.soft_nms's
+    defaults -- and class_agnostic; any other key is refused.  The selection state of an image lives in LDS while max(rows) * C <=
+    SOFT_NMS_LDS_CAPACITY, in a workspace allocated here beyond that."""
+    lib = L.load()
+    cfg = dict(nms_cfg)
+    typ = cfg.pop('type', 'nms')
+    if typ != 'soft_nms':
+        raise L.LoftHipError(f"multiclass_soft_nms_batched: nms type '{typ}' is not 'soft_nms'; type='nms' runs for a batch in "
+                             'multiclass_nms_batched')
+    agnostic = bool(cfg.pop('class_agnostic', False))
+    if 'iou_threshold' not in cfg:
+        raise L.LoftHipError("multiclass_soft_nms_batched: nms_cfg has no 'iou_threshold'")
+    iou_thr = float(cfg.pop('iou_threshold'))
+    sigma, min_score = float(cfg.pop('sigma', 0.5)), float(cfg.pop('min_score', 1e-3))
+    method = cfg.pop('method', 'linear')
+    if cfg:
+        raise L.LoftHipError(f"multiclass_soft_nms_batched: unknown key '{sorted(cfg)[0]}' in nms_cfg (type, iou_threshold, sigma, "
+                             'min_score, method, class_agnostic)')
+    if method not in _SOFT_NMS_METHODS:
+        raise L.LoftHipError(f"multiclass_soft_nms_batched: method '{method}' is none of {sorted(_SOFT_NMS_METHODS)}")
+    max_per_img = int(max_per_img)
+    if max_per_img <= 0 or max_per_img > TOPK_MAX:
+        raise L.LoftHipError(f'multiclass_soft_nms_batched: max_per_img = {max_per_img} outside 1 .. {TOPK_MAX} (kernels.TOPK_MAX)')
+    L.dev_check(bboxes, scores)
+    dev = scores.device
+    offs = [int(v) for v in (roi_off.tolist() if torch.is_tensor(roi_off) else roi_off)]
+    R, C = int(scores.shape[0]), int(scores.shape[1]) - 1
+    B = len(offs) - 1
+    if B < 1 or C < 1 or offs[0] != 0 or offs[-1] != R or any(a > b for a, b in zip(offs, offs[1:])):
+        raise L.LoftHipError(f'multiclass_soft_nms_batched: roi_off {offs} does not cut the {R} rows of scores {tuple(scores.shape)} into images')
+    box_cols = int(bboxes.shape[1]) if bboxes.dim() == 2 else -1
+    if bboxes.shape[0] != R or box_cols not in (4, 4 * C):
+        raise L.LoftHipError(f'multiclass_soft_nms_batched: bboxes {tuple(bboxes.shape)} for scores {tuple(scores.shape)}: [R, 4C] or [R, 4] needed')
+    if R * C >= 2 ** 31:
+        raise L.LoftHipError(f'multiclass_soft_nms_batched: {R} rows x {C} classes: flat indices are 32-bit')
+    scores, bboxes = scores.float().contiguous(), bboxes.float().contiguous()
+    if torch.is_tensor(roi_off):
+        L.dev_check(roi_off)
+        roi_off_d = roi_off.to(torch.int64).contiguous()
+    else:
+        roi_off_d = h2d(offs, torch.int64, dev)
+    max_rows = max(b - a for a, b in zip(offs, offs[1:]))
+    nbytes = lib.loft_soft_nms_batched_workspace_bytes(B, max_rows * C)       # 0: the LDS form
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    dets = torch.empty(B, max_per_img, 5, dtype=torch.float32, device=dev)
+    labels = torch.empty(B, max_per_img, dtype=torch.int64, device=dev)
+    counts = torch.empty(B, dtype=torch.int64, device=dev)
+    rois = torch.empty(B * max_per_img, 5, dtype=torch.float32, device=dev)
+    L.check(lib.loft_soft_nms_batched(L.ptr(scores), L.ptr(bboxes), box_cols, L.ptr(roi_off_d), B, C, max_rows, float(score_thr),
+                                      int(agnostic), iou_thr, sigma, min_score, _SOFT_NMS_METHODS[method], max_per_img,
+                                      L.ptr(ws) if ws is not None else None, L.ptr(dets), L.ptr(labels), L.ptr(counts), L.ptr(rois),
+                                      L.stream()), 'loft_soft_nms_batched')
     return dets, labels, counts, rois
 
 

@@ -869,13 +869,15 @@ class LoftRoIHead(nn.Module):
         return det_bboxes, det_labels, sel.float(), offsets
 
     @torch.no_grad()
-    def batch_test_device(self, x, proposals, img_metas):
+    def batch_test_device(self, x, proposals, img_metas, soft_nms_batched=False):
         """simple_test_device for the B images of a batch (x: their features; proposals: simple_test_rpn's (props [B,P,5], counts
         [B])) -> (det_bboxes [N,5], det_labels [N], class-selected mask logits [N,S,S], decoded offsets [N,2], det_counts int64 [B]
         on the host): image-major, inside an image the order simple_test_device gives.  Every head runs ONCE -- the bbox head over
         the RoIs of all images (padded proposal rows dropped), the mask and offset heads over all detections -- and the selection
         between them is kernels.multiclass_nms_batched: the host reads the proposal counts and the detection counts, nothing else.
-        simple_test_device's refusals, and images of one img_shape; the NMS must be type='nms' (soft-NMS is sequential per image)."""
+        simple_test_device's refusals, and images of one img_shape; the NMS must be type='nms' (soft-NMS is sequential per image)
+        unless ``soft_nms_batched`` is given: then a type='soft_nms' config selects through kernels.multiclass_soft_nms_batched (one
+        workgroup per image, the per-image results bit for bit); with type='nms' the keyword changes nothing."""
         cfg = self.test_cfg
         if cfg.get('paste_min_score') is not None:
             raise ValueError('test_cfg.rcnn.paste_min_score filters simple_test\'s results; batch_test_device returns every detection')
@@ -910,7 +912,8 @@ class LoftRoIHead(nn.Module):
         scores = torch.softmax(cls_score, dim=1)
         rr = rois[:, 1:].repeat_interleave(bbox_pred.shape[1] // 4, dim=0)
         bboxes = self.bbox_head.bbox_coder.decode(rr, bbox_pred.reshape(-1, 4), max_shape=img_shape).view(rois.shape[0], -1)
-        dets, labels, det_counts, det_rois = K.multiclass_nms_batched(bboxes, scores, off, cfg.score_thr, cfg.nms, cfg.max_per_img)
+        select = K.multiclass_soft_nms_batched if soft_nms_batched and cfg.nms.get('type', 'nms') == 'soft_nms' else K.multiclass_nms_batched
+        dets, labels, det_counts, det_rois = select(bboxes, scores, off, cfg.score_thr, cfg.nms, cfg.max_per_img)
         det_counts = det_counts.cpu().numpy()
         N = int(det_counts.sum())
         if N == 0:                                  # no head runs: the logits' S is not known, they are [0,0,0]

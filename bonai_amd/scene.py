@@ -79,10 +79,12 @@ class SceneDetector:
     SceneResult.  ``tile``: side or (h, w), multiples of 32 (default: ``cfg.data.test.img_scale`` when a config is given, else the
     dataset's 1024); ``overlap``: pixels neighbouring tiles share at least; ``merge_thr``, ``border``: the rule of the module
     docstring; ``footprints``: also the footprints' strings.  ``cfg``: the model's Config -- its test pipeline must not ask for
-    test-time augmentation (the tiles' views would have to be merged before the scene's tiles are: not built)."""
+    test-time augmentation (the tiles' views would have to be merged before the scene's tiles are: not built).  ``batch``: tiles per
+    pass through the model; above 1 the NMS must be type='nms', or type='soft_nms' with ``soft_nms_batched=True`` (the selection
+    of kernels.multiclass_soft_nms_batched, passed on to LoftRoIHead.batch_test_device)."""
 
     def __init__(self, model, tile=None, overlap=256, merge_thr=0.5, border=2, footprints=False, cfg=None,
-                 mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375), to_rgb=True, batch=1):
+                 mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375), to_rgb=True, batch=1, soft_nms_batched=False):
         if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or not 1 <= batch <= PREP_CHUNK:
             raise ValueError(f'batch must be an integer in 1 .. {PREP_CHUNK} (the tiles prepared per launch), got {batch!r}')
         tcfg = ((cfg.get('data') or {}).get('test') if cfg is not None else None) or {}
@@ -112,9 +114,9 @@ class SceneDetector:
         if not roi.with_mask:
             raise ValueError('whole-scene inference merges detections on their masks: the model has no mask head')
         nms_type = dict(rcnn.get('nms') or {}).get('type', 'nms')
-        if batch > 1 and nms_type != 'nms':
+        if batch > 1 and nms_type != 'nms' and not (soft_nms_batched and nms_type == 'soft_nms'):
             raise ValueError(f"test_cfg.rcnn.nms type '{nms_type}' is sequential per image: tiles go through the model in batches "
-                             "only with type='nms'; use batch=1")
+                             "only with type='nms'; use batch=1, or soft_nms_batched=True for type='soft_nms'")
         if not 0 <= float(merge_thr) or int(border) < 0:
             raise ValueError(f'merge_thr >= 0 and border >= 0 needed, got {merge_thr} and {border}')
         if cfg is not None and cfg.get('img_norm_cfg'):
@@ -122,6 +124,7 @@ class SceneDetector:
             mean, std, to_rgb = tuple(nc['mean']), tuple(nc['std']), bool(nc.get('to_rgb', True))
         self.model, self.overlap, self.merge_thr, self.border = model, int(overlap), float(merge_thr), int(border)
         self.footprints, self.batch = bool(footprints), int(batch)
+        self.soft_nms_batched = bool(soft_nms_batched)
         self.mean, self.std, self.to_rgb = tuple(float(v) for v in mean), tuple(float(v) for v in std), bool(to_rgb)
 
     # ------------------------------------------------------------------ tiles
@@ -155,7 +158,7 @@ class SceneDetector:
                     # tile_grid shifts the last tile of an axis inward, and a scene below the tile size is one row or column of equal
                     # tiles: the tiles of a scene share img_shape
                     assert all(m['img_shape'] == metas[0]['img_shape'] for m in metas), [m['img_shape'] for m in metas]
-                    d, l, m, o, n = self.model.roi_head.batch_test_device(x, props, metas)
+                    d, l, m, o, n = self.model.roi_head.batch_test_device(x, props, metas, **({'soft_nms_batched': True} if self.soft_nms_batched else {}))
                     if d.shape[0] == 0:                # no head ran: every tile of the group gets the empty tuple
                         dets.extend((d, l, m, o) for _ in metas)
                         continue

@@ -626,6 +626,21 @@ int loft_soft_nms(const float* boxes, const float* scores, int64_t n, float iou_
                   void* workspace, float* dets, int64_t* inds, int* n_out, void* stream);
 int loft_mask_paste(const float* logits, const float* boxes, int N, int S, int img_h, int img_w, float thr, uint8_t* out,
                     void* stream);
+/* loft_soft_nms_batched (nms.hip): multiclass_nms with a soft_nms config (bbox_nms.py:5-69 -> batched_nms -> soft_nms -> [:max_num])
+ * for the B images of a batch, one workgroup per image, nothing read back.  scores fp32 [R, C+1] (background last), bboxes fp32
+ * [R, box_cols], box_cols = 4C or 4; roi_off_dev int64 [B+1] row offsets; max_rows: the rows of the longest image, known to the host.
+ * Candidates are scores > score_thr in ascending flat index row * C + class; the shift is label * (max over the image's candidate
+ * coordinates + 1) unless class_agnostic; method 0 naive, 1 linear, 2 gaussian; selection stops after max_per_img (1 .. 4096) slots.
+ * -> dets fp32 [B, max_per_img, 5] (the unshifted box, the decayed score), labels int64 [B, max_per_img], counts int64 [B], rois fp32
+ * [B * max_per_img, 5] = (image, box) of all detections image-major without gaps; everything past the counts is zero.
+ * max_rows * C <= LOFT_SOFT_NMS_LDS_CAPACITY: the selection state lives in LDS and workspace may be NULL; else in
+ * loft_soft_nms_batched_workspace_bytes(B, max_rows * C) bytes of workspace.  An image longer than max_rows yields no detections. */
+#define LOFT_SOFT_NMS_LDS_CAPACITY 4096
+int64_t loft_soft_nms_batched_workspace_bytes(int B, int64_t max_candidates);
+int loft_soft_nms_batched(const float* scores, const float* bboxes, int box_cols, const int64_t* roi_off_dev, int B, int C,
+                          int64_t max_rows, float score_thr, int class_agnostic, float iou_thr, float sigma, float min_score,
+                          int method, int max_per_img, void* workspace, float* dets, int64_t* labels, int64_t* counts, float* rois,
+                          void* stream);
 /* loft_mask_translate: footprint bitmaps from roof bitmaps and predicted offsets -- what the reference's evaluation does on polygons
  * through the external bstool package (tools/bonai/bonai_evaluation.py:64-91 BSPklParser(..., offset_model='footprint2roof'):
  * footprint = roof translated by -offset; offsets are the third element of the result tuples of mmdet/apis/test.py:53-72).

@@ -3,12 +3,14 @@
 (bonai_amd/scene.py; an extension -- the reference's tools/bonai/bonai_test.py delegates this step to an external package).
 
     python tools/scene.py CONFIG [CHECKPOINT] IMAGE [IMAGE ...] --out results.pkl [--tile N] [--overlap N] [--merge-thr F]
-                          [--footprints] [--batch N] [--hard-nms]
+                          [--footprints] [--batch N] [--hard-nms | --batched-soft-nms]
 
 Images are decoded with PIL as the dataset decodes its tiles.  ``--out`` pickles one result tuple per image in simple_test's
 layout for an image of the scene's size: (bbox_results, segm_results as COCO RLE, offset_results[, footprint RLE with --footprints]).
 ``--batch N`` (1 .. 16) sends the tiles through the model N at a time (LoftRoIHead.batch_test_device); it needs test_cfg.rcnn.nms of
-type 'nms' -- soft-NMS is sequential per image -- and ``--hard-nms`` replaces the config's by type='nms' at the same iou_threshold.
+type 'nms' -- soft-NMS is sequential per image -- and ``--hard-nms`` replaces the config's by type='nms' at the same iou_threshold;
+``--batched-soft-nms`` instead keeps the config's soft-NMS and runs it for the tiles of a batch at once, one workgroup per tile
+(kernels.multiclass_soft_nms_batched).  The two exclude each other.
 A first positional argument after CONFIG that ends in .pth / .pt is the checkpoint; without one the weights are the seeded
 initialisation (a smoke run).
 """
@@ -35,7 +37,11 @@ def main():
     ap.add_argument('--batch', type=int, default=1, help='tiles per pass through the model, 1 .. 16 (default 1: every tile alone)')
     ap.add_argument('--hard-nms', action='store_true',
                     help="test_cfg.rcnn.nms becomes type='nms' at the config's iou_threshold (--batch > 1 refuses soft-NMS)")
+    ap.add_argument('--batched-soft-nms', action='store_true',
+                    help="with --batch > 1 a type='soft_nms' config stays as it is and is selected for all tiles of a batch in one launch")
     args = ap.parse_args()
+    if args.hard_nms and args.batched_soft_nms:
+        ap.error('--batched-soft-nms keeps the soft-NMS of the config that --hard-nms replaces: give one of them')
     ckpt = args.paths[0] if args.paths[0].endswith(('.pth', '.pt')) else None
     images = args.paths[1:] if ckpt else args.paths
     if not images:
@@ -56,7 +62,7 @@ def main():
         load_checkpoint(model, ckpt, strict=True)
     model = model.cuda().eval()
     det = SceneDetector(model, tile=args.tile, overlap=args.overlap, merge_thr=args.merge_thr, footprints=args.footprints, cfg=cfg,
-                        batch=args.batch)
+                        batch=args.batch, soft_nms_batched=args.batched_soft_nms)
     results = []
     for path in images:
         t0 = time.time()
