@@ -32,6 +32,7 @@
 // deeper prefetch does; the next step is a 256-row, 8-wave tile with fragment double-buffering, not more stages.
 #include "loft_common.h"
 #include <algorithm>
+#include <iterator>
 #include <type_traits>
 #include "../../include/loft_hip.h"
 #include <stdlib.h>
@@ -729,190 +730,228 @@ LOFT_EXPORT int loft_bneck_tail_bf16(const void* t1, const void* w2, const float
     return 0;
 }
 
-int loft_launch_conv_tap_pipe(const ConvArgs& a, int groups, int mode, int var, int mj, int nw_force, hipStream_t s, int ring32 = 0);     // conv_pipe.hip
+// =====================================================================================
+// Host side of the forward / data-gradient tap convolution.  ONE decision, conv_tap_plan, made before anything is launched or any
+// device attribute is read:  arguments valid -> the kernel (the pinned LOFT_CONV_* code, conv_auto_kernel's or conv_planes_kernel's
+// choice) -> conv_refusal: does that kernel serve this launch, and why not -> tile, rows, grid -> the stream form.  The three entry
+// points build their ConvArgs with conv_args_build (conv_tap.h) from the plan's rows and add only what is their own; the plan is
+// all conv_pipe.hip gets besides the arguments, and loft_conv_tap_form returns it without a launch.
+// A NEW KERNEL FORM is registered in four places: its code in include/loft_hip.h, its tile in conv_kernel_tile, what it does not
+// serve in conv_refusal, its template instance in conv_tap_launch (lockstep) or loft_launch_conv_tap_pipe (pipelined) -- plus a
+// row in conv_auto_kernel if the dispatcher is to choose it, and its cases in tests/test_conv_forms_cpu.py.
+// =====================================================================================
+int loft_launch_conv_tap_pipe(ConvArgs a, const ConvTapPlan& p, hipStream_t s);     // conv_pipe.hip
+
+// What a launch asks for besides its shape.
+struct ConvAsk {
+    int variant;              // LOFT_CONV_* code | LOFT_CONV_FLAG_* | experiment bits 12-15 (include/loft_hip.h)
+    int head_c4;              // > 0: a narrow 1x1 head of that many outputs in the epilogue (ConvArgs block 5)
+    bool residual, mask;
+    int nterms;               // > 0: operand planes, fp32 epilogue (loft_conv_tap_planes)
+    int par_n;                // 1: the four taps of a 2x2 deconvolution as four N tiles (loft_deconv2x2_bf16)
+};
+
+static bool conv_is_pipelined(int k) { return k == LOFT_CONV_PIPE256 || (k >= LOFT_CONV_STREAM256 && k <= LOFT_CONV_LEANX); }
+
+// Tile of a kernel code: pixels x couts.  (PATCH64: a 16 x 16 pixel patch; T128x64 is the only tile that need not divide Cout.)
+static void conv_kernel_tile(int k, int Cout, int* tile_m, int* tile_n) {
+    *tile_m = 256; *tile_n = 256;
+    switch (k) {
+    case LOFT_CONV_STREAM256: *tile_n = Cout % 256 ? 128 : 256; break;      // Cout = 128 (mod 256): 128-cout tiles, three-stage ring
+    case LOFT_CONV_STREAM256N: *tile_n = 128; break;
+    case LOFT_CONV_STREAM128: *tile_m = 128; break;
+    case LOFT_CONV_STREAM64: *tile_m = 64; break;
+    case LOFT_CONV_STREAM64N: *tile_m = 64; *tile_n = 128; break;
+    case LOFT_CONV_T128_SINGLE: case LOFT_CONV_T128_FAST: case LOFT_CONV_T128: *tile_m = 128; *tile_n = 128; break;
+    case LOFT_CONV_T128x64: *tile_m = 128; *tile_n = 64; break;
+    case LOFT_CONV_PATCH64: *tile_n = 64; break;
+    default: break;
+    }
+}
+
+// Does a launch on tile_m x tile_n tiles fill the chip?  192 workgroups, measured on MI355X.
+static bool conv_fills(const ConvShape& g, long M, int tile_m, int tile_n) {
+    return (long)loft_cdiv(M, tile_m) * (g.Cout / tile_n) * g.groups >= 192;
+}
+
+// What the halo patch kernel serves: 64 -> 64 channels, one group, unit strides, a same-size map, 4..9 taps within -1..1, bf16 out.
+static bool conv_patch64_ok(const ConvShape& g) {
+    bool ok = g.Cin == 64 && g.Cout == 64 && g.T >= 4 && g.T <= 9 && g.groups == 1 && g.ss == 1 && g.os == 1 && g.OH == g.IH &&
+              g.OW == g.IW && g.OHf == g.OH && g.OWf == g.OW && g.oo_y == 0 && g.oo_x == 0 && !g.out_f32 && !g.accumulate;
+    for (int t = 0; t < g.T && ok; ++t) ok = g.dy[t] >= -1 && g.dy[t] <= 1 && g.dx[t] >= -1 && g.dx[t] <= 1;
+    return ok;
+}
+
+static bool conv_two_tiles(const ConvShape& g, const ConvAsk& q) {      // residual AND mask tiles staged in LDS: both halves of a double buffer
+    return q.residual && q.mask && !g.out_f32 && g.os == 1 && g.OHf == g.OH && g.OWf == g.OW;
+}
+static bool conv_staged_out(const ConvShape& g, int variant) { return !(variant & LOFT_CONV_FLAG_NO_STAGED_OUT) && !g.accumulate; }
+
+// LOFT_CONV_AUTO: the dispatcher's choice, a pure function of the shape (M = B * OH * OW unpadded rows).  Thresholds measured on
+// MI355X; tests/test_conv_tap_form_cpu.py holds one shape on either side of each.
+static int conv_auto_kernel(const ConvShape& g, const ConvAsk& q, long M) {
+    if (conv_patch64_ok(g) && M >= 65536) return LOFT_CONV_PATCH64;
+    const long Kdim = (long)g.T * g.Cin;
+    const bool deepk = Kdim >= 1024;      // >= 16 K-steps: hoisted addressing (FAST) amortises its prologue (round 2: 8x64x64 1024->256 32.8 vs 34.6 us)
+    const bool c256 = g.Cout % 256 == 0, c128 = g.Cout % 128 == 0;
+    // (bf16 outputs only: the pipelined kernels' epilogue collects the output tile in LDS; fp32 / accumulating launches keep the lockstep kernels)
+    const bool b16 = !g.out_f32 && !g.accumulate;
+    // too few 256-pixel tiles to fill the chip (layer3's 64 x 64 maps): the stream kernel on 128-pixel tiles
+    if (c256 && b16 && !conv_fills(g, M, 256, 256) && conv_fills(g, M, 128, 256) && Kdim >= 1024) return LOFT_CONV_STREAM128;
+    // layer4's 32 x 32 maps
+    if (c256 && b16 && !conv_fills(g, M, 128, 256) && conv_fills(g, M, 64, 256) && Kdim >= 2048) return LOFT_CONV_STREAM64;
+    // 256 couts on a 32 x 32 map: 64-pixel x 128-cout tiles fill the chip (P5 3x3: 50 -> 2x as many workgroups)
+    if (c256 && b16 && !conv_fills(g, M, 64, 256) && conv_fills(g, M, 64, 128) && Kdim >= 2048) return LOFT_CONV_STREAM64N;
+    // the software-pipelined kernel with the LDS-staged, row-contiguous epilogue (conv_pipe.hip; +26..43 % over the lockstep
+    // 256-tile kernel on the 3x3 / FC shapes, +15..35 % over the 128-tile kernels on the K-shallow 1x1s)
+    if (c256 && b16 && conv_fills(g, M, 256, 256)) return LOFT_CONV_STREAM256;
+    if (c256 && conv_fills(g, M, 256, 256) && Kdim >= 512) return deepk ? LOFT_CONV_T256_FAST : LOFT_CONV_T256;
+    // 128-cout tiles of the stream kernel (layer2's 3x3 convs and their data gradients)
+    if (c128 && b16 && Kdim >= 1024 && conv_fills(g, M, 256, 128)) return LOFT_CONV_STREAM256;
+    if (!c128) return LOFT_CONV_T128x64;
+    // (single-stage form at four workgroups per CU: K <= 512 since round 2 -- 8x128x128 512->128: 37.8 against 48.8 us)
+    if (!conv_two_tiles(g, q) && conv_staged_out(g, q.variant) && Kdim <= 512) return LOFT_CONV_T128_SINGLE;
+    return deepk ? LOFT_CONV_T128_FAST : LOFT_CONV_T128;
+}
+
+// Plane launches (M = the PADDED row count): the largest of the stream kernel's tiles that still fills the chip -- conv_fills, as
+// conv_auto_kernel.  Where the two rules DIFFER: no K-depth thresholds here, the rows count with their padding, and a launch that
+// fills the chip on no tile stays on the stream kernel's smallest one (64 x 128) instead of leaving for a lockstep kernel.
+static int conv_planes_kernel(const ConvShape& g, long M) {
+    if (g.Cout % 256) return conv_fills(g, M, 256, 128) ? LOFT_CONV_STREAM256 : LOFT_CONV_STREAM64N;
+    if (conv_fills(g, M, 256, 256)) return LOFT_CONV_STREAM256;
+    if (conv_fills(g, M, 128, 256)) return LOFT_CONV_STREAM128;
+    return conv_fills(g, M, 64, 256) ? LOFT_CONV_STREAM64 : LOFT_CONV_STREAM64N;
+}
+
+// The experiment instances conv_pipe.hip compiles (VAR): of PIPE256 and of STREAM256's 256 x 256 tile only.
+static bool conv_var_exists(int k, int Cout, int var) {
+    static const int pipe[] = {1, 4, 5, 8, 10, 12}, stream[] = {1, 2, 3, 4, 8, 9, 10, 12, 14, 15};
+    if (k == LOFT_CONV_PIPE256) return std::find(std::begin(pipe), std::end(pipe), var) != std::end(pipe);
+    if (k == LOFT_CONV_STREAM256 && Cout % 256 == 0) return std::find(std::begin(stream), std::end(stream), var) != std::end(stream);
+    return false;
+}
+
+// Whether kernel k (a LOFT_CONV_* code, not AUTO) serves the launch: nullptr, or why not.  EVERY refusal of a kernel code, flag,
+// head, par_n or plane launch is here (M = the row count the kernel enumerates).
+static const char* conv_refusal(int k, const ConvShape& g, const ConvAsk& q, long M) {
+    const int var = (q.variant >> 12) & 0xf;
+    const bool tap_major = q.variant & LOFT_CONV_FLAG_TAP_MAJOR, krot = (q.variant & LOFT_CONV_FLAG_KROT) && !tap_major;
+    const bool stream = k == LOFT_CONV_STREAM256 || k == LOFT_CONV_STREAM128 || k == LOFT_CONV_STREAM64;
+    if (q.head_c4) {
+        if (q.head_c4 < 4 || q.head_c4 > 32 || q.head_c4 % 4) return "a head has 4, 8, .. 32 outputs";
+        if (g.Cout != 256 || g.groups != 1 || g.out_f32 || g.accumulate || q.nterms) return "a head reads ONE staged 16-bit tile of all 256 couts";
+        if (q.mask) return "the head reads the tile before a mask would apply";
+        if (q.variant & ~0xff) return "no flags or experiment bits with a head";
+        if (!stream) return "a head is served by the staged epilogue of the 256-cout stream tiles only";
+    }
+    if (q.nterms && !(q.variant == LOFT_CONV_AUTO && (stream || k == LOFT_CONV_STREAM64N) && g.Cout % 128 == 0 && q.nterms <= CONV_MAX_TERMS &&
+                      q.nterms * g.T <= 64 && !g.accumulate))
+        return "planes: the stream kernel's tiles, Cout % 128 == 0, nterms <= 8, nterms * T <= 64";
+    if (q.par_n && !(k == LOFT_CONV_STREAM256 && q.variant == LOFT_CONV_AUTO && g.Cout == 256 && g.T == 1 && g.os == 2 && !q.residual &&
+                     !q.mask && !q.nterms && conv_fills(g, M, 256, 256)))
+        return "par_n: the 256 x 256 stream tile, Cout == 256, >= 192 pixel tiles, one tap, os == 2, no residual or mask";
+    if (conv_is_pipelined(k)) {
+        if (!q.nterms && (g.out_f32 || g.accumulate)) return "pipelined kernels collect a 16-bit output tile in LDS";
+        if (g.Cout % 256 && !((k == LOFT_CONV_STREAM256 || q.nterms) && g.Cout % 128 == 0)) return "Cout % 256 (STREAM256, and planes on 64 x 128 tiles: % 128)";
+        if (tap_major && (k == LOFT_CONV_LEAN || k == LOFT_CONV_LEANX || k == LOFT_CONV_RING32 || k == LOFT_CONV_W4)) return "a chunk-major schedule";
+        if (krot && (k == LOFT_CONV_RING32 || k == LOFT_CONV_W4)) return "no chunk rotation in RING32 / W4";
+        if (var && !conv_var_exists(k, g.Cout, var)) return "no such experiment instance";
+        return nullptr;
+    }
+    if (q.nterms || q.par_n) return "planes and par_n are the stream kernel's";
+    switch (k) {
+    case LOFT_CONV_T256_FAST: case LOFT_CONV_T256: return g.Cout % 256 ? "Cout % 256" : nullptr;
+    case LOFT_CONV_T128_SINGLE: if (conv_two_tiles(g, q)) return "one LDS tile only: not residual AND mask tiles";      // fall through
+    case LOFT_CONV_T128_FAST: case LOFT_CONV_T128: return g.Cout % 128 ? "Cout % 128" : nullptr;
+    case LOFT_CONV_T128x64: return nullptr;
+    case LOFT_CONV_PATCH64: return conv_patch64_ok(g) ? nullptr : "64 -> 64 channels, stride 1, same-size map, 4..9 taps within -1..1";
+    default: return "no such kernel";
+    }
+}
+
+// The instance of the two-stage 256 x 256 stream schedule that launches for STREAM256, pinned or chosen, under the process-wide
+// form (loft_conv_stream_form: 0 the round-2 schedule, 1 XFIRST, 2 LEAN, 3 LEANX).  LEAN is chunk-major only: a TAP-MAJOR launch
+// under form 2 or 3 falls back to form 0 (not to 1); plane launches have the round-2 and the LEAN instance only.
+static int conv_stream_instance(const ConvTapPlan& p, const ConvAsk& q, int form) {
+    if (p.kernel != LOFT_CONV_STREAM256 || p.tile_n != 256 || p.var) return p.kernel;
+    form &= 3;
+    if (q.nterms) return form >= 2 ? LOFT_CONV_LEAN : LOFT_CONV_STREAM256;
+    if ((q.variant & LOFT_CONV_FLAG_TAP_MAJOR) && form >= 2) return LOFT_CONV_STREAM256;
+    return form == 0 ? LOFT_CONV_STREAM256 : form == 1 ? LOFT_CONV_XFIRST : form == 2 ? LOFT_CONV_LEAN : LOFT_CONV_LEANX;
+}
+
+// -> 0 and *p (p->kernel == 0: no output pixel, nothing to launch), or hipErrorInvalidValue.  Host arithmetic only.
+static int conv_tap_plan(const ConvShape& g, const ConvAsk& q, int stream_form, ConvTapPlan* p) {
+    *p = ConvTapPlan{};
+    int k = q.variant & 0xff;
+    if (g.T < 1 || g.T > CONV_MAX_TAPS || (g.Cin % BK) || (g.Cout % 4) || g.groups < 1 || k > LOFT_CONV_LEANX || (q.variant & ~0x3ffff))
+        return (int)hipErrorInvalidValue;
+    const long M = (long)g.B * g.OH * g.OW;
+    if (M <= 0) return 0;
+    if (M > 0x7fffffffL) return (int)hipErrorInvalidValue;
+    const ConvRows blocks = conv_rows(g, q.variant & LOFT_CONV_FLAG_NO_PIXMAJOR, q.variant & LOFT_CONV_FLAG_NO_ROI_BLOCKS);
+    if (q.par_n) k = LOFT_CONV_STREAM256;
+    else if (q.nterms) k = conv_planes_kernel(g, blocks.M);
+    else if (k == LOFT_CONV_AUTO) k = conv_auto_kernel(g, q, M);
+    // rows: the pipelined kernels enumerate RoI blocks, the lockstep FAST 256 tile position-major rows over all RoIs, the rest (RoI, pixel)
+    p->rows = conv_is_pipelined(k) ? blocks : conv_rows(g, k != LOFT_CONV_T256_FAST || (q.variant & LOFT_CONV_FLAG_NO_PIXMAJOR), true);
+    if (p->rows.M > 0x7fffffffL || conv_refusal(k, g, q, p->rows.M)) return (int)hipErrorInvalidValue;
+    p->kernel = k;
+    p->var = conv_is_pipelined(k) ? (q.variant >> 12) & 0xf : 0;
+    conv_kernel_tile(k, g.Cout, &p->tile_m, &p->tile_n);
+    if (k == LOFT_CONV_PATCH64) p->grid = dim3((unsigned)((long)g.B * loft_cdiv(g.OW, 16) * loft_cdiv(g.OH, 16)));      // patches; the launch caps them at the CUs
+    else p->grid = dim3(loft_cdiv(p->rows.M, p->tile_m), (q.par_n ? 4 : 1) * loft_cdiv(g.Cout, p->tile_n), g.groups);
+    p->kernel = conv_stream_instance(*p, q, stream_form);
+    return 0;
+}
 
 struct ConvHead { const void* w; const float* b; float* out; int c4; };
 
-static int conv_tap_bf16_impl(const void* src, const void* wgt, const float* bias, const void* residual,
-                              const void* relu_mask, void* out,
-                              const void* zero_page, int B, int IH, int IW, int Cin, int Cout, int OH, int OW,
-                              int OHf, int OWf, int os, int oo_y, int oo_x, int ss, int T, const int* dy_host,
-                              const int* dx_host, const int* wt_host, int relu, int out_f32, int accumulate,
-                              int groups, int64_t src_gs, int64_t wgt_gs, int64_t out_gs, int64_t bias_gs,
-                              int variant, void* stream, const ConvHead* head) {
-    if (T < 1 || T > CONV_MAX_TAPS || (Cin % BK) || (Cout % 4) || groups < 1) return (int)hipErrorInvalidValue;
-    const int kern = variant & 0xff;                 // LOFT_CONV_* kernel selector, 0 = the dispatcher's own choice
-    if (kern > LOFT_CONV_LEANX || (variant & ~0x3ffff)) return (int)hipErrorInvalidValue;
-    ConvArgs a;
-    a.src = (const bf16_t*)src; a.wgt = (const bf16_t*)wgt; a.bias = bias; a.residual = (const bf16_t*)residual; a.mask = (const bf16_t*)relu_mask;
-    a.out = out; a.zero_page = (const bf16_t*)zero_page;
-    a.B = B; a.IH = IH; a.IW = IW; a.Cin = Cin; a.Cout = Cout; a.OH = OH; a.OW = OW; a.OHf = OHf; a.OWf = OWf;
-    a.os = os; a.oo_y = oo_y; a.oo_x = oo_x; a.ss = ss; a.T = T;
-    for (int t = 0; t < T; ++t) { a.dy[t] = dy_host[t]; a.dx[t] = dx_host[t]; a.wt[t] = wt_host[t]; }
-    a.relu = relu; a.out_f32 = out_f32; a.accumulate = accumulate;
-    a.src_gs = src_gs; a.wgt_gs = wgt_gs; a.out_gs = out_gs; a.bias_gs = bias_gs;
-    a.trace = nullptr;
-    a.nterms = 0; a.amax_x = nullptr; a.amax_w = nullptr; a.amax_out = nullptr;
-    a.head_w = nullptr; a.head_b = nullptr; a.head_out = nullptr; a.head_c4 = 0; a.par_n = 0;
-    if (head) {
-        // (served by the staged epilogue of the 256-cout stream tiles only; anything else: the caller launches the head itself)
-        if (!head->w || !head->b || !head->out || head->c4 < 4 || head->c4 > 32 || (head->c4 % 4) || Cout != 256 || groups != 1 ||
-            out_f32 || accumulate || (variant & ~0xff) || relu_mask)      // (the head reads the tile before a mask would apply)
-            return (int)hipErrorInvalidValue;
-        a.head_w = (const bf16_t*)head->w; a.head_b = head->b; a.head_out = head->out; a.head_c4 = head->c4;
-    }
-    fastdiv_setup((unsigned)(OH * OW), &a.ohw_mul, &a.ohw_sh);
-    fastdiv_setup((unsigned)OW, &a.ow_mul, &a.ow_sh);
-    fastdiv_setup((unsigned)B, &a.b_mul, &a.b_sh);
-    const long M = (long)B * OH * OW;
-    if (M <= 0) return 0;
-    if (M > 0x7fffffffL) return (int)hipErrorInvalidValue;
-    a.M = (int)M;
-    hipStream_t s = (hipStream_t)stream;
-    {
-        bool p64 = Cin == 64 && Cout == 64 && T >= 4 && T <= 9 && groups == 1 && ss == 1 && os == 1 && OH == IH && OW == IW &&
-                   OHf == OH && OWf == OW && oo_y == 0 && oo_x == 0 && !out_f32 && !accumulate;
-        for (int t = 0; t < T && p64; ++t) p64 = dy_host[t] >= -1 && dy_host[t] <= 1 && dx_host[t] >= -1 && dx_host[t] <= 1;
-        if (kern == LOFT_CONV_PATCH64 && !p64) return (int)hipErrorInvalidValue;
-        if (kern == LOFT_CONV_PATCH64 || (kern == LOFT_CONV_AUTO && p64 && M >= 65536)) {
-            if (head) return (int)hipErrorInvalidValue;
-            Conv64Args c;
-            c.src = a.src; c.wgt = a.wgt; c.bias = bias; c.residual = a.residual; c.mask = a.mask; c.out = (bf16_t*)out;
-            c.zero_page = a.zero_page; c.B = B; c.H = OH; c.W = OW; c.T = T; c.relu = relu;
-            for (int t = 0; t < T; ++t) { c.dy[t] = dy_host[t]; c.dx[t] = dx_host[t]; c.wt[t] = wt_host[t]; }
-            const int ptx = (OW + 15) / 16, pty = (OH + 15) / 16;
-            const long np = (long)B * ptx * pty;
-            int cus = 256;
-            { int dev = 0; hipGetDevice(&dev); hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); }
-            const long nb = np < cus ? np : cus;
-            const size_t lds_bytes = (size_t)T * 64 * 128 + 2 * 41 * 8 * 128;
-            hipFuncSetAttribute((const void*)conv64_patch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            hipLaunchKernelGGL(conv64_patch_kernel, dim3((unsigned)nb), dim3(512), lds_bytes, s, c, ptx, pty, (int)np);
-            LOFT_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-    // Thresholds below are measured on MI355X; `variant` overrides the kernel choice for tests and A/B timing.
-    // staged_out: the 128x128 kernels collect a dense bf16 output tile in LDS and store it row-contiguously.
-    a.staged_out = !(variant & LOFT_CONV_FLAG_NO_STAGED_OUT) && !accumulate;
-    a.pixmajor = 0;
-    // Channel-tile-fastest order when the activation is the big operand (it does not fit the 4 MiB L2 of an XCD but the packed
-    // weights do): every channel tile of a pixel tile then runs back to back on one XCD and the pixel tile comes from HBM once
-    // instead of once per channel tile.
-    a.nfast = !(variant & LOFT_CONV_FLAG_NO_NFAST);
-    const long big_blocks = (long)loft_cdiv(M, 256) * (Cout / 256) * groups;
-    const long Kdim = (long)T * Cin;
-    const bool deepk = Kdim >= 1024;      // >= 16 K-steps: hoisted addressing (FAST) amortises its prologue (round 2: 8x64x64 1024->256 32.8 vs 34.6 us)
-    // pixel-major enumeration of RoI-map tiles (FAST / pipelined 256-row kernels): taps that leave the map are skipped per tile
-    const bool pix_ok = !(variant & LOFT_CONV_FLAG_NO_PIXMAJOR) && T > 1 && T <= 32 && B >= 256 && OH * OW <= 1024 && os == 1 &&
-                        ss == 1 && OHf == OH && OWf == OW;
-    int k = kern;
-    if (k == LOFT_CONV_AUTO) {
-        const long half_blocks = (long)loft_cdiv(M, 128) * (Cout / 256) * groups;
-        if (Cout % 256 == 0 && big_blocks < 192 && half_blocks >= 192 && Kdim >= 1024 && !out_f32 && !accumulate) {
-            // too few 256-pixel tiles to fill the chip (layer3's 64 x 64 maps): the stream kernel on 128-pixel tiles
-            k = LOFT_CONV_STREAM128;
-        } else if (Cout % 256 == 0 && half_blocks < 192 && (long)loft_cdiv(M, 64) * (Cout / 256) * groups >= 192 && Kdim >= 2048 &&
-                   !out_f32 && !accumulate) {
-            k = LOFT_CONV_STREAM64;           // layer4's 32 x 32 maps
-        } else if (Cout % 256 == 0 && (long)loft_cdiv(M, 64) * (Cout / 256) * groups < 192 &&
-                   (long)loft_cdiv(M, 64) * (Cout / 128) * groups >= 192 && Kdim >= 2048 && !out_f32 && !accumulate) {
-            k = LOFT_CONV_STREAM64N;          // 256 couts on a 32 x 32 map: 64-pixel x 128-cout tiles fill the chip (P5 3x3: 50 -> 2x as many workgroups)
-        } else if (Cout % 256 == 0 && big_blocks >= 192 && !out_f32 && !accumulate) {
-            // bf16 output: the software-pipelined kernel with the LDS-staged, row-contiguous epilogue (conv_pipe.hip; +26..43 %
-            // over the lockstep 256-tile kernel on the 3x3 / FC shapes, +15..35 % over the 128-tile kernels on the K-shallow 1x1s)
-            k = LOFT_CONV_STREAM256;
-        } else if (Cout % 256 == 0 && big_blocks >= 192 && Kdim >= 512) {
-            k = deepk ? LOFT_CONV_T256_FAST : LOFT_CONV_T256;
-        }
-        else if (Cout % 128 == 0 && !out_f32 && !accumulate && Kdim >= 1024 && (long)loft_cdiv(M, 256) * (Cout / 128) * groups >= 192) {
-            k = LOFT_CONV_STREAM256;          // 128-cout tiles of the stream kernel (layer2's 3x3 convs and their data gradients)
-        } else if (Cout % 128 == 0) {
-            const bool dense_out = !out_f32 && os == 1 && OHf == OH && OWf == OW;
-            const bool two_tiles = residual && relu_mask && dense_out;        // needs both halves of the double buffer
-            // (single-stage form at four workgroups per CU: K <= 512 since round 2 -- 8x128x128 512->128: 37.8 against 48.8 us)
-            if (!two_tiles && a.staged_out && Kdim <= 512) k = LOFT_CONV_T128_SINGLE;
-            else k = deepk ? LOFT_CONV_T128_FAST : LOFT_CONV_T128;
-        } else k = LOFT_CONV_T128x64;
-    }
-    switch (k) {
-    case LOFT_CONV_LEANX:
-    case LOFT_CONV_LEAN:
-    case LOFT_CONV_XFIRST:
-    case LOFT_CONV_W4:
-    case LOFT_CONV_RING32:
-    case LOFT_CONV_ROLES256:
-    case LOFT_CONV_STREAM256N:
-    case LOFT_CONV_STREAM64N:
-    case LOFT_CONV_STREAM64:
-    case LOFT_CONV_STREAM128:
-    case LOFT_CONV_STREAM256:
-    case LOFT_CONV_PIPE256:
-        // software-pipelined 256x256 kernels (conv_pipe.hip)
-        // (bf16 outputs only: their epilogue collects the output tile in LDS; fp32 / accumulating launches keep the lockstep kernels)
-        if ((Cout % 256 && !(k == LOFT_CONV_STREAM256 && Cout % 128 == 0)) || out_f32 || accumulate) return (int)hipErrorInvalidValue;
-        if (k == LOFT_CONV_STREAM256N && ((variant >> 12) & 0xf)) return (int)hipErrorInvalidValue;
-        if (head && !(k == LOFT_CONV_STREAM256 || k == LOFT_CONV_STREAM128 || k == LOFT_CONV_STREAM64)) return (int)hipErrorInvalidValue;
-        a.pixmajor = pix_ok;
-        a.pm_S = B; a.pm_P = OH * OW;
-        if (pix_ok) {
-            // RoI blocks of >= 256 rows per pixel position (ConvArgs::pm_S): padded row count nb * P * S >= P * B
-            const int nb = (variant & LOFT_CONV_FLAG_NO_ROI_BLOCKS) ? 1 : std::max(1, B / 256);
-            a.pm_S = (B + nb - 1) / nb;
-            const long Mp = (long)nb * a.pm_P * a.pm_S;
-            if (Mp > 0x7fffffffL) return (int)hipErrorInvalidValue;
-            a.M = (int)Mp;
-        }
-        fastdiv_setup((unsigned)a.pm_S, &a.pms_mul, &a.pms_sh);
-        fastdiv_setup((unsigned)a.pm_P, &a.pmp_mul, &a.pmp_sh);
-        a.trace = (variant & 0x1000) ? const_cast<float*>(bias) : nullptr;      // experiment bits 12-15 (conv_pipe.hip VAR); TRACE
-        if (a.trace) a.bias = nullptr;                                          // borrows the bias pointer for its buffer
+// loft_conv_tap_bf16 / _v / _head: plan, build, set what is this entry point's own (head, K order, trace), launch.
+static int conv_tap_launch(const ConvOperands& ops, const ConvShape& g, int variant, const ConvHead* head, hipStream_t s) {
+    if (head && (!head->w || !head->b || !head->out || head->c4 < 1)) return (int)hipErrorInvalidValue;
+    const ConvAsk q{variant, head ? head->c4 : 0, ops.residual != nullptr, ops.mask != nullptr, 0, 0};
+    ConvTapPlan p;
+    if (int e = conv_tap_plan(g, q, loft_conv_stream_form(-1), &p)) return e;
+    if (!p.kernel) return 0;
+    // staged_out: the 128x128 kernels collect a dense bf16 output tile in LDS and store it row-contiguously.  nfast: channel-tile-
+    // fastest order when the activation is the big operand (it does not fit the 4 MiB L2 of an XCD but the packed weights do):
+    // every channel tile of a pixel tile then runs back to back on one XCD and the pixel tile comes from HBM once.
+    ConvArgs a = conv_args_build(ops, g, p.rows, conv_staged_out(g, variant), !(variant & LOFT_CONV_FLAG_NO_NFAST));
+    if (head) { a.head_w = (const bf16_t*)head->w; a.head_b = head->b; a.head_out = head->out; a.head_c4 = head->c4; }
+    if (conv_is_pipelined(p.kernel)) {
         a.tap_major = (variant & LOFT_CONV_FLAG_TAP_MAJOR) ? 1 : 0;
         a.krot = (variant & LOFT_CONV_FLAG_KROT) && !a.tap_major ? 1 : 0;
-        if (k == LOFT_CONV_ROLES256 && (Cout % 256 || ((variant >> 12) & 0xf))) return (int)hipErrorInvalidValue;
-        if ((k == LOFT_CONV_RING32 || k == LOFT_CONV_W4 || k >= LOFT_CONV_XFIRST) && (Cout % 256 || ((variant >> 12) & 0xf))) return (int)hipErrorInvalidValue;
-        return loft_launch_conv_tap_pipe(a, groups, k == LOFT_CONV_PIPE256 ? 0 : (k == LOFT_CONV_ROLES256 ? 2 : 1), (variant >> 12) & 0xf,
-                                         k == LOFT_CONV_STREAM128 ? 2 : ((k == LOFT_CONV_STREAM64 || k == LOFT_CONV_STREAM64N) ? 1 : 4),
-                                         (k == LOFT_CONV_STREAM64N || k == LOFT_CONV_STREAM256N) ? 1 : 0, s, k == LOFT_CONV_RING32 ? 1 : (k == LOFT_CONV_W4 ? 2 : (k == LOFT_CONV_XFIRST ? 3 : (k == LOFT_CONV_LEAN ? 4 : (k == LOFT_CONV_LEANX ? 5 : 0)))));
-    case LOFT_CONV_T256_FAST:
-    case LOFT_CONV_T256: {
-        if (head) return (int)hipErrorInvalidValue;
-        // 256x256 tile, 8 waves of 128x64: half the LDS traffic per FLOP of the 128x128 form; only when it still
-        // fills the 256 CUs and K is deep enough (>= 8 K-steps) to amortise the one-block-per-CU prologue/epilogue.
-        // (Round-1 measurements of rejected forms -- 4 waves of 128x128, 256x128 tiles with 4 waves, LDS-staged output -- are in
-        //  DESIGN.md; note that round 1's pipelining experiments ran with a compiler-inserted vmcnt(0) in front of every
-        //  K-step's fragment reads, see conv_tap_kernel.)
-        if (Cout % 256) return (int)hipErrorInvalidValue;
-        dim3 grid(loft_cdiv(M, 256), Cout / 256, groups);
-        if (k == LOFT_CONV_T256_FAST) {
-            a.pixmajor = pix_ok;
-            hipLaunchKernelGGL((conv_tap_kernel<256, 256, 2, 4, 2, true>), grid, dim3(512), 0, s, a);
-        } else hipLaunchKernelGGL((conv_tap_kernel<256, 256, 2, 4>), grid, dim3(512), 0, s, a);
+        if (p.var & 1) { a.trace = const_cast<float*>(ops.bias); a.bias = nullptr; }      // TRACE experiments borrow the bias pointer for their buffer
+        return loft_launch_conv_tap_pipe(a, p, s);
+    }
+    switch (p.kernel) {
+    case LOFT_CONV_PATCH64: {
+        Conv64Args c;
+        c.src = a.src; c.wgt = a.wgt; c.bias = a.bias; c.residual = a.residual; c.mask = a.mask; c.out = (bf16_t*)a.out;
+        c.zero_page = a.zero_page; c.B = g.B; c.H = g.OH; c.W = g.OW; c.T = g.T; c.relu = g.relu;
+        for (int t = 0; t < g.T; ++t) { c.dy[t] = g.dy[t]; c.dx[t] = g.dx[t]; c.wt[t] = g.wt[t]; }
+        int cus = 256;
+        { int dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); }
+        const unsigned np = p.grid.x, nb = np < (unsigned)cus ? np : (unsigned)cus;
+        const size_t lds_bytes = (size_t)g.T * 64 * 128 + 2 * 41 * 8 * 128;
+        (void)hipFuncSetAttribute((const void*)conv64_patch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipLaunchKernelGGL(conv64_patch_kernel, dim3(nb), dim3(512), lds_bytes, s, c, loft_cdiv(g.OW, 16), loft_cdiv(g.OH, 16), (int)np);
         break;
     }
-    case LOFT_CONV_T128_SINGLE:
-    case LOFT_CONV_T128_FAST:
-    case LOFT_CONV_T128: {
-        if (Cout % 128 || head) return (int)hipErrorInvalidValue;
-        dim3 grid(loft_cdiv(M, 128), Cout / 128, groups);
-        if (k == LOFT_CONV_T128_SINGLE) {
-            const bool dense_out = !out_f32 && os == 1 && OHf == OH && OWf == OW;
-            if (residual && relu_mask && dense_out) return (int)hipErrorInvalidValue;   // one LDS tile only
-            hipLaunchKernelGGL((conv_tap_kernel<128, 128, 2, 2, 1>), grid, dim3(256), 0, s, a);
-        } else if (k == LOFT_CONV_T128_FAST)
-            hipLaunchKernelGGL((conv_tap_kernel<128, 128, 2, 2, 2, true>), grid, dim3(256), 0, s, a);
-        else
-            hipLaunchKernelGGL((conv_tap_kernel<128, 128, 2, 2>), grid, dim3(256), 0, s, a);
-        break;
-    }
-    case LOFT_CONV_T128x64: {
-        if (head) return (int)hipErrorInvalidValue;
-        dim3 grid(loft_cdiv(M, 128), loft_cdiv(Cout, 64), groups);
-        hipLaunchKernelGGL((conv_tap_kernel<128, 64, 4, 1>), grid, dim3(256), 0, s, a);
-        break;
-    }
-    default:
-        return (int)hipErrorInvalidValue;
+    // 256x256 tile, 8 waves of 128x64: half the LDS traffic per FLOP of the 128x128 form; only when it still
+    // fills the 256 CUs and K is deep enough (>= 8 K-steps) to amortise the one-block-per-CU prologue/epilogue.
+    // (Round-1 measurements of rejected forms -- 4 waves of 128x128, 256x128 tiles with 4 waves, LDS-staged output -- are in
+    //  DESIGN.md; note that round 1's pipelining experiments ran with a compiler-inserted vmcnt(0) in front of every
+    //  K-step's fragment reads, see conv_tap_kernel.)
+    case LOFT_CONV_T256_FAST: hipLaunchKernelGGL((conv_tap_kernel<256, 256, 2, 4, 2, true>), p.grid, dim3(512), 0, s, a); break;
+    case LOFT_CONV_T256: hipLaunchKernelGGL((conv_tap_kernel<256, 256, 2, 4>), p.grid, dim3(512), 0, s, a); break;
+    case LOFT_CONV_T128_SINGLE: hipLaunchKernelGGL((conv_tap_kernel<128, 128, 2, 2, 1>), p.grid, dim3(256), 0, s, a); break;
+    case LOFT_CONV_T128_FAST: hipLaunchKernelGGL((conv_tap_kernel<128, 128, 2, 2, 2, true>), p.grid, dim3(256), 0, s, a); break;
+    case LOFT_CONV_T128: hipLaunchKernelGGL((conv_tap_kernel<128, 128, 2, 2>), p.grid, dim3(256), 0, s, a); break;
+    case LOFT_CONV_T128x64: hipLaunchKernelGGL((conv_tap_kernel<128, 64, 4, 1>), p.grid, dim3(256), 0, s, a); break;
+    default: return (int)hipErrorInvalidValue;
     }
     LOFT_LAUNCH_CHECK();
     return 0;
@@ -925,9 +964,9 @@ LOFT_EXPORT int loft_conv_tap_bf16_v(const void* src, const void* wgt, const flo
                                      const int* dx_host, const int* wt_host, int relu, int out_f32, int accumulate,
                                      int groups, int64_t src_gs, int64_t wgt_gs, int64_t out_gs, int64_t bias_gs,
                                      int variant, void* stream) {
-    return conv_tap_bf16_impl(src, wgt, bias, residual, relu_mask, out, zero_page, B, IH, IW, Cin, Cout, OH, OW, OHf, OWf, os, oo_y,
-                              oo_x, ss, T, dy_host, dx_host, wt_host, relu, out_f32, accumulate, groups, src_gs, wgt_gs, out_gs,
-                              bias_gs, variant, stream, nullptr);
+    const ConvShape g{B, IH, IW, Cin, Cout, OH, OW, OHf, OWf, os, oo_y, oo_x, ss, T, dy_host, dx_host, wt_host, relu, out_f32, accumulate,
+                      groups, src_gs, wgt_gs, out_gs, bias_gs};
+    return conv_tap_launch(ConvOperands{src, wgt, bias, residual, relu_mask, out, zero_page}, g, variant, nullptr, (hipStream_t)stream);
 }
 
 // The same launch with a NARROW 1x1 HEAD on its output computed in the epilogue (ConvArgs block 5): head_out[pixel][n] = head_b[n] +
@@ -941,8 +980,8 @@ LOFT_EXPORT int loft_conv_tap_bf16_head(const void* src, const void* wgt, const 
                                         const int* dx_host, const int* wt_host, int relu, const void* head_w, const float* head_b,
                                         float* head_out, int head_c4, void* stream) {
     const ConvHead h{head_w, head_b, head_out, head_c4};
-    return conv_tap_bf16_impl(src, wgt, bias, residual, relu_mask, out, zero_page, B, IH, IW, Cin, Cout, OH, OW, OHf, OWf, os, oo_y,
-                              oo_x, ss, T, dy_host, dx_host, wt_host, relu, 0, 0, 1, 0, 0, 0, 0, LOFT_CONV_AUTO, stream, &h);
+    const ConvShape g{B, IH, IW, Cin, Cout, OH, OW, OHf, OWf, os, oo_y, oo_x, ss, T, dy_host, dx_host, wt_host, relu, 0, 0, 1, 0, 0, 0, 0};
+    return conv_tap_launch(ConvOperands{src, wgt, bias, residual, relu_mask, out, zero_page}, g, LOFT_CONV_AUTO, &h, (hipStream_t)stream);
 }
 
 // ConvTranspose2d(kernel 2, stride 2) + bias (+ ReLU) as ONE launch of the stream kernel (fcn_mask_head.py:121-124, the mask head's
@@ -953,32 +992,16 @@ LOFT_EXPORT int loft_conv_tap_bf16_head(const void* src, const void* wgt, const 
 LOFT_EXPORT int loft_deconv2x2_bf16(const void* src, const void* wgt, const float* bias, void* out, const void* zero_page, int B, int H,
                                     int W, int Cin, int Cout, int relu, const void* head_w, const float* head_b, float* head_out,
                                     int head_c4, void* stream) {
-    if (Cout != 256 || (Cin % BK) || B < 1 || H < 1 || W < 1) return (int)hipErrorInvalidValue;
-    const long M = (long)B * H * W;
-    if (M > 0x7fffffffL || loft_cdiv(M, 256) < 192) return (int)hipErrorInvalidValue;
-    if (head_w && (!head_b || !head_out || head_c4 < 4 || head_c4 > 32 || (head_c4 % 4))) return (int)hipErrorInvalidValue;
-    ConvArgs a;
-    a.src = (const bf16_t*)src; a.wgt = (const bf16_t*)wgt; a.bias = bias; a.residual = nullptr; a.mask = nullptr;
-    a.out = out; a.zero_page = (const bf16_t*)zero_page;
-    a.B = B; a.IH = H; a.IW = W; a.Cin = Cin; a.Cout = Cout; a.OH = H; a.OW = W; a.OHf = 2 * H; a.OWf = 2 * W;
-    a.os = 2; a.oo_y = 0; a.oo_x = 0; a.ss = 1; a.T = 1;
-    a.dy[0] = 0; a.dx[0] = 0; a.wt[0] = 0;
-    a.relu = relu; a.out_f32 = 0; a.accumulate = 0;
-    a.src_gs = 0; a.wgt_gs = 0; a.out_gs = 0; a.bias_gs = 0;
-    a.trace = nullptr;
-    a.nterms = 0; a.amax_x = nullptr; a.amax_w = nullptr; a.amax_out = nullptr;
-    a.head_w = (const bf16_t*)head_w; a.head_b = head_b; a.head_out = head_out; a.head_c4 = head_w ? head_c4 : 0;
+    if (B < 1 || H < 1 || W < 1 || (head_w && (!head_b || !head_out || head_c4 < 1))) return (int)hipErrorInvalidValue;
+    static const int zero = 0;                     // one tap at offset 0, weight tap 0: N tile p takes weight rows [256 p, 256 p + 256)
+    const ConvShape g{B, H, W, Cin, Cout, H, W, 2 * H, 2 * W, 2, 0, 0, 1, 1, &zero, &zero, &zero, relu, 0, 0, 1, 0, 0, 0, 0};
+    const ConvAsk q{LOFT_CONV_AUTO, head_w ? head_c4 : 0, false, false, 0, 1};
+    ConvTapPlan p;
+    if (int e = conv_tap_plan(g, q, loft_conv_stream_form(-1), &p)) return e;
+    ConvArgs a = conv_args_build(ConvOperands{src, wgt, bias, nullptr, nullptr, out, zero_page}, g, p.rows, 1, 1);
+    if (head_w) { a.head_w = (const bf16_t*)head_w; a.head_b = head_b; a.head_out = head_out; a.head_c4 = head_c4; }
     a.par_n = 1;
-    fastdiv_setup((unsigned)(H * W), &a.ohw_mul, &a.ohw_sh);
-    fastdiv_setup((unsigned)W, &a.ow_mul, &a.ow_sh);
-    fastdiv_setup((unsigned)B, &a.b_mul, &a.b_sh);
-    a.M = (int)M;
-    a.staged_out = 1; a.pixmajor = 0; a.nfast = 1;
-    a.pm_S = B; a.pm_P = H * W;
-    fastdiv_setup((unsigned)a.pm_S, &a.pms_mul, &a.pms_sh);
-    fastdiv_setup((unsigned)a.pm_P, &a.pmp_mul, &a.pmp_sh);
-    a.tap_major = 0; a.krot = 0;
-    return loft_launch_conv_tap_pipe(a, 1, 1, 0, 4, 0, (hipStream_t)stream, 0);
+    return loft_launch_conv_tap_pipe(a, p, (hipStream_t)stream);
 }
 
 LOFT_EXPORT int loft_conv_tap_bf16(const void* src, const void* wgt, const float* bias, const void* residual,
@@ -1008,63 +1031,43 @@ LOFT_EXPORT int loft_conv_tap_planes(const void* src, const void* wgt, const flo
                                      int64_t src_gs, int64_t wgt_gs, int64_t out_gs, int64_t bias_gs, int nterms,
                                      const int* xpl_host, const int* wpl_host, int64_t x_ps, int64_t w_ps,
                                      const float* amax_x, const float* amax_w, float* amax_out, void* stream) {
-    if (T < 1 || T > CONV_MAX_TAPS || (Cin % BK) || (Cout % 128) || groups < 1 || nterms < 1 || nterms > CONV_MAX_TERMS ||
-        nterms * T > 64 || (amax_x == nullptr) != (amax_w == nullptr))
-        return (int)hipErrorInvalidValue;
-    ConvArgs a;
-    a.src = (const bf16_t*)src; a.wgt = (const bf16_t*)wgt; a.bias = bias; a.residual = (const bf16_t*)residual;
-    a.mask = (const bf16_t*)relu_mask; a.out = out; a.zero_page = (const bf16_t*)zero_page;
-    a.B = B; a.IH = IH; a.IW = IW; a.Cin = Cin; a.Cout = Cout; a.OH = OH; a.OW = OW; a.OHf = OHf; a.OWf = OWf;
-    a.os = os; a.oo_y = oo_y; a.oo_x = oo_x; a.ss = ss; a.T = T;
+    if (nterms < 1 || (amax_x == nullptr) != (amax_w == nullptr)) return (int)hipErrorInvalidValue;
+    const ConvShape g{B, IH, IW, Cin, Cout, OH, OW, OHf, OWf, os, oo_y, oo_x, ss, T, dy_host, dx_host, wt_host, relu, 1, 0, groups,
+                      src_gs, wgt_gs, out_gs, bias_gs};
+    const int form = loft_conv_stream_form(-1);
+    ConvTapPlan p;
+    if (int e = conv_tap_plan(g, ConvAsk{LOFT_CONV_AUTO, 0, residual != nullptr, relu_mask != nullptr, nterms, 0}, form, &p)) return e;
+    if (!p.kernel) return 0;
+    // (form bit 2: the direct, un-staged fp32 epilogue -- A/B of the round-6 LDS-staged one of the 256 x 256 tile)
+    ConvArgs a = conv_args_build(ConvOperands{src, wgt, bias, residual, relu_mask, out, zero_page}, g, p.rows, (form & 4) ? 0 : 1, 1);
     long max_a = 0, max_w = 0;                    // largest tap offsets (elements): plane offset + tap offset must fit 32 bits
     for (int t = 0; t < T; ++t) {
-        a.dy[t] = dy_host[t]; a.dx[t] = dx_host[t]; a.wt[t] = wt_host[t];
         max_a = std::max(max_a, labs(((long)dy_host[t] * IW + dx_host[t]) * Cin));
         max_w = std::max(max_w, (long)wt_host[t] * Cout * Cin);
     }
     a.nterms = nterms;
-    for (int p = 0; p < nterms; ++p) {
-        const long xo = (long)xpl_host[p] * x_ps, wo = (long)wpl_host[p] * w_ps;
-        if (xpl_host[p] < 0 || wpl_host[p] < 0 || xo + max_a > 0x7fffffffL || wo + max_w > 0x7fffffffL) return (int)hipErrorInvalidValue;
-        a.xoff[p] = (int)xo; a.woff[p] = (int)wo;
+    for (int i = 0; i < nterms; ++i) {
+        const long xo = (long)xpl_host[i] * x_ps, wo = (long)wpl_host[i] * w_ps;
+        if (xpl_host[i] < 0 || wpl_host[i] < 0 || xo + max_a > 0x7fffffffL || wo + max_w > 0x7fffffffL) return (int)hipErrorInvalidValue;
+        a.xoff[i] = (int)xo; a.woff[i] = (int)wo;
     }
     a.amax_x = amax_x; a.amax_w = amax_w; a.amax_out = amax_out;
-    a.head_w = nullptr; a.head_b = nullptr; a.head_out = nullptr; a.head_c4 = 0; a.par_n = 0;
-    a.relu = relu; a.out_f32 = 1; a.accumulate = 0; a.staged_out = 0;
-    a.src_gs = src_gs; a.wgt_gs = wgt_gs; a.out_gs = out_gs; a.bias_gs = bias_gs;
-    a.trace = nullptr;
-    fastdiv_setup((unsigned)(OH * OW), &a.ohw_mul, &a.ohw_sh);
-    fastdiv_setup((unsigned)OW, &a.ow_mul, &a.ow_sh);
-    fastdiv_setup((unsigned)B, &a.b_mul, &a.b_sh);
-    const long M = (long)B * OH * OW;
-    if (M <= 0) return 0;
-    if (M > 0x7fffffffL) return (int)hipErrorInvalidValue;
-    a.M = (int)M;
-    a.nfast = 1; a.tap_major = 0; a.krot = 0;
-    const bool pix_ok = T > 1 && T <= 32 && B >= 256 && OH * OW <= 1024 && os == 1 && ss == 1 && OHf == OH && OWf == OW;
-    a.pixmajor = pix_ok;
-    a.pm_S = B; a.pm_P = OH * OW;
-    if (pix_ok) {
-        const int nb = std::max(1, B / 256);
-        a.pm_S = (B + nb - 1) / nb;
-        const long Mp = (long)nb * a.pm_P * a.pm_S;
-        if (Mp > 0x7fffffffL) return (int)hipErrorInvalidValue;
-        a.M = (int)Mp;
-    }
-    fastdiv_setup((unsigned)a.pm_S, &a.pms_mul, &a.pms_sh);
-    fastdiv_setup((unsigned)a.pm_P, &a.pmp_mul, &a.pmp_sh);
-    // tile shape: the largest of the stream kernel's tiles that still gives ~192 workgroups (as loft_conv_tap_bf16_v)
-    int mj, nwf = 0;
-    if (Cout % 256 == 0) {
-        const long nt = (long)(Cout / 256) * groups;
-        if (loft_cdiv(a.M, 256) * nt >= 192) mj = 4;
-        else if (loft_cdiv(a.M, 128) * nt >= 192) mj = 2;
-        else if (loft_cdiv(a.M, 64) * nt >= 192) mj = 1;
-        else { mj = 1; nwf = 1; }
-    } else {
-        mj = (long)loft_cdiv(a.M, 256) * (Cout / 128) * groups >= 192 ? 4 : 1;
-    }
-    return loft_launch_conv_tap_pipe(a, groups, 1, 0, mj, nwf, (hipStream_t)stream);
+    return loft_launch_conv_tap_pipe(a, p, (hipStream_t)stream);
+}
+
+// Which kernel loft_conv_tap_bf16_v / loft_conv_tap_bf16_head (head_c4 > 0) / loft_conv_tap_planes (nterms > 0) launches for these
+// arguments: conv_tap_plan itself, the function those launches call.  No device is touched.  include/loft_hip.h has the contract.
+LOFT_EXPORT int loft_conv_tap_form(int B, int IH, int IW, int Cin, int Cout, int OH, int OW, int OHf, int OWf, int os, int oo_y, int oo_x,
+                                   int ss, int T, const int* dy_host, const int* dx_host, const int* wt_host, int out_f32,
+                                   int accumulate, int groups, int variant, int head_c4, int residual, int relu_mask, int nterms,
+                                   int* form_out) {
+    if (nterms < 0 || head_c4 < 0 || (nterms && (variant != LOFT_CONV_AUTO || accumulate))) return (int)hipErrorInvalidValue;
+    const ConvShape g{B, IH, IW, Cin, Cout, OH, OW, OHf, OWf, os, oo_y, oo_x, ss, T, dy_host, dx_host, wt_host, 0, nterms ? 1 : out_f32,
+                      accumulate, groups, 0, 0, 0, 0};
+    ConvTapPlan p;
+    if (int e = conv_tap_plan(g, ConvAsk{variant, head_c4, residual != 0, relu_mask != 0, nterms, 0}, loft_conv_stream_form(-1), &p)) return e;
+    form_out[0] = p.kernel; form_out[1] = p.tile_m; form_out[2] = p.tile_n; form_out[3] = p.rows.pixmajor; form_out[4] = (int)p.rows.M;
+    return 0;
 }
 
 // =====================================================================================

@@ -1970,35 +1970,15 @@ LOFT_EXPORT int loft_conv_stream_form(int form) {
     return prev;
 }
 
-// host side: launched from loft_conv_tap_bf16_v (conv_mfma.hip).  Requires Cout % 256 == 0, Cin % 64 == 0, T <= 16.
-int loft_launch_conv_tap_pipe(const ConvArgs& a_in, int groups, int mode, int var, int mj, int nw_force, hipStream_t s, int ring32) {
-    ConvArgs a = a_in;
-    if (a.nterms) a.staged_out = g_f32_direct_epilogue ? 0 : 1;      // plane launches: the LDS-staged fp32 epilogue of the 256 x 256 tile
-    const bool w4 = ring32 == 2;                       // (2: the four-wave kernel, LOFT_CONV_W4)
-    const bool xfirst = ring32 == 3 || ring32 == 5;    // (3: the activations-first stream schedule, LOFT_CONV_XFIRST)
-    const bool lean = ring32 == 4 || ring32 == 5;      // (4: LOFT_CONV_LEAN, 5: LOFT_CONV_LEANX = LEAN + XFIRST)
-    if (w4 || xfirst || lean) ring32 = 0;
-    if ((xfirst || lean) && !(mode == 1 && var == 0 && mj == 4 && nw_force == 0 && a.Cout % 256 == 0 && !a.nterms))
-        return (int)hipErrorInvalidValue;
-    if (lean && a.tap_major) return (int)hipErrorInvalidValue;
-    if (w4 && !(mode == 1 && var == 0 && mj == 4 && nw_force == 0 && a.Cout % 256 == 0 && !a.tap_major && !a.krot && !a.nterms))
-        return (int)hipErrorInvalidValue;
-    if (ring32 && !(mode == 1 && var == 0 && mj == 4 && nw_force == 0 && a.Cout % 256 == 0 && !a.tap_major && !a.krot && !a.nterms))
-        return (int)hipErrorInvalidValue;
-    if (mj != 4 && !((mj == 2 || mj == 1) && mode == 1 && var == 0)) return (int)hipErrorInvalidValue;
-    if (mode == 2 && (a.Cout % 256 || nw_force == 1)) return (int)hipErrorInvalidValue;
-    const int nw = nw_force == 1 ? 1 : (a.Cout % 256 == 0 ? 2 : 1);       // 128-cout tiles: Cout = 128 (mod 256), or by choice with 64-pixel tiles
-    if (nw == 1 && !(mode == 1 && var == 0 && (mj == 4 || mj == 1) && a.Cout % 128 == 0)) return (int)hipErrorInvalidValue;
-    if (a.nterms && !(mode == 1 && var == 0 && a.nterms <= CONV_MAX_TERMS && a.nterms * a.T <= 64)) return (int)hipErrorInvalidValue;
-    if (a.par_n && !(mode == 1 && var == 0 && mj == 4 && nw == 2 && a.Cout == 256 && !w4 && !ring32 && !a.nterms && a.T == 1 && a.os == 2 &&
-                     !a.residual && !a.mask && a.staged_out))
-        return (int)hipErrorInvalidValue;
-    dim3 grid(loft_cdiv(a.M, 64 * mj), (a.par_n ? 4 : 1) * (a.Cout / (128 * nw)), groups);
+// host side: launched from conv_mfma.hip (conv_tap_launch, loft_deconv2x2_bf16, loft_conv_tap_planes) with the plan conv_tap_plan
+// made -- what a kernel serves, the tile, the grid and the stream form were decided THERE.  Here: the fields of ConvArgs that depend
+// on the grid, the packed tap tables, and the ONE place where the template instance is chosen from the plan.
+int loft_launch_conv_tap_pipe(ConvArgs a, const ConvTapPlan& p, hipStream_t s) {
+    const dim3 grid = p.grid;
     fastdiv_setup(grid.x * grid.y, &a.gxy_mul, &a.gxy_sh);
     fastdiv_setup(grid.x, &a.gx_mul, &a.gx_sh);
     fastdiv_setup(grid.y, &a.gy_mul, &a.gy_sh);
     a.pointwise = a.T == 1 && a.dy[0] == 0 && a.dx[0] == 0 && a.ss == 1 && !a.pixmajor && a.IH == a.OH && a.IW == a.OW;
-    a.dy_pk = a.dx_pk = a.wt_pk = 0ull;
     a.pk_ok = 1;
     for (int t = 0; t < a.T; ++t) {
         if (a.dy[t] < -8 || a.dy[t] > 7 || a.dx[t] < -8 || a.dx[t] > 7 || a.wt[t] < 0 || a.wt[t] > 15) { a.pk_ok = 0; break; }
@@ -2006,43 +1986,31 @@ int loft_launch_conv_tap_pipe(const ConvArgs& a_in, int groups, int mode, int va
         a.dx_pk |= (unsigned long long)(a.dx[t] + 8) << (4 * t);
         a.wt_pk |= (unsigned long long)a.wt[t] << (4 * t);
     }
-#define PIPE_LAUNCH(M_, V_) hipLaunchKernelGGL((conv_tap_pipe_kernel<M_, V_>), grid, dim3(512), 0, s, a)
+    const bool n128 = p.tile_n == 128;      // 128-cout tiles of the 256-pixel stream tile: the three-stage ring (NW = 1)
+    // conv_tap_pipe_kernel<MODE, VAR, MJ = tile pixels / 64, NW = tile couts / 128, PL, R32, XF, LEAN>
+#define PIPE_LAUNCH(...) hipLaunchKernelGGL((conv_tap_pipe_kernel<__VA_ARGS__>), grid, dim3(512), 0, s, a)
     if (a.nterms) {                   // operand planes: the stream schedule's five tile shapes with the fp32 epilogue
-        if (nw == 1 && mj == 1) hipLaunchKernelGGL((conv_tap_pipe_kernel<1, 0, 1, 1, true>), grid, dim3(512), 0, s, a);
-        else if (nw == 1) hipLaunchKernelGGL((conv_tap_pipe_kernel<1, 0, 4, 1, true>), grid, dim3(512), 0, s, a);
-        else if (mj == 2) hipLaunchKernelGGL((conv_tap_pipe_kernel<1, 0, 2, 2, true>), grid, dim3(512), 0, s, a);
-        else if (mj == 1) hipLaunchKernelGGL((conv_tap_pipe_kernel<1, 0, 1, 2, true>), grid, dim3(512), 0, s, a);
-        else if (g_stream_form >= 2 && !a.tap_major)        // (the lean instruction stream, as for the 16-bit launches: same sums, same order)
-            hipLaunchKernelGGL((conv_tap_pipe_kernel<1, 0, 4, 2, true, false, false, true>), grid, dim3(512), 0, s, a);
-        else hipLaunchKernelGGL((conv_tap_pipe_kernel<1, 0, 4, 2, true>), grid, dim3(512), 0, s, a);
-    } else if (xfirst && lean) {
-        hipLaunchKernelGGL((conv_tap_pipe_kernel<1, 0, 4, 2, false, false, true, true>), grid, dim3(512), 0, s, a);
-    } else if (lean) {
-        hipLaunchKernelGGL((conv_tap_pipe_kernel<1, 0, 4, 2, false, false, false, true>), grid, dim3(512), 0, s, a);
-    } else if (xfirst) {
-        hipLaunchKernelGGL((conv_tap_pipe_kernel<1, 0, 4, 2, false, false, true>), grid, dim3(512), 0, s, a);
-    } else if (w4) {
-        hipLaunchKernelGGL(conv_tap_w4_kernel<0>, grid, dim3(256), 0, s, a);
-    } else if (ring32) {
-        hipLaunchKernelGGL((conv_tap_pipe_kernel<1, 0, 4, 2, false, true>), grid, dim3(512), 0, s, a);
-    } else if (nw == 1 && mj == 1) {
-        hipLaunchKernelGGL((conv_tap_pipe_kernel<1, 0, 1, 1>), grid, dim3(512), 0, s, a);
-    } else if (nw == 1) {
-        hipLaunchKernelGGL((conv_tap_pipe_kernel<1, 0, 4, 1>), grid, dim3(512), 0, s, a);
-    } else if (mode == 1 && mj == 2) {
-        hipLaunchKernelGGL((conv_tap_pipe_kernel<1, 0, 2>), grid, dim3(512), 0, s, a);
-    } else if (mode == 1 && mj == 1) {
-        hipLaunchKernelGGL((conv_tap_pipe_kernel<1, 0, 1>), grid, dim3(512), 0, s, a);
-    } else if (mode == 2) {
-        if (var != 0) return (int)hipErrorInvalidValue;
-        PIPE_LAUNCH(2, 0);
-    } else if (mode == 1 && var == 0 && g_stream_form != 0 && !(a.tap_major && (g_stream_form == 2 || g_stream_form == 3))) {
-        // the process-wide default form of the two-stage 256 x 256 stream schedule (loft_conv_stream_form: same-box A/B of a whole step)
-        if (g_stream_form == 1) hipLaunchKernelGGL((conv_tap_pipe_kernel<1, 0, 4, 2, false, false, true>), grid, dim3(512), 0, s, a);
-        else if (g_stream_form == 2) hipLaunchKernelGGL((conv_tap_pipe_kernel<1, 0, 4, 2, false, false, false, true>), grid, dim3(512), 0, s, a);
-        else hipLaunchKernelGGL((conv_tap_pipe_kernel<1, 0, 4, 2, false, false, true, true>), grid, dim3(512), 0, s, a);
-    } else if (mode == 1) {
-        switch (var) {
+        if (p.kernel == LOFT_CONV_STREAM64N) PIPE_LAUNCH(1, 0, 1, 1, true);
+        else if (p.kernel == LOFT_CONV_STREAM256 && n128) PIPE_LAUNCH(1, 0, 4, 1, true);
+        else if (p.kernel == LOFT_CONV_STREAM128) PIPE_LAUNCH(1, 0, 2, 2, true);
+        else if (p.kernel == LOFT_CONV_STREAM64) PIPE_LAUNCH(1, 0, 1, 2, true);
+        else if (p.kernel == LOFT_CONV_LEAN) PIPE_LAUNCH(1, 0, 4, 2, true, false, false, true);      // (same sums, same order)
+        else if (p.kernel == LOFT_CONV_STREAM256) PIPE_LAUNCH(1, 0, 4, 2, true);
+        else return (int)hipErrorInvalidValue;
+    } else switch (p.kernel) {
+    case LOFT_CONV_LEANX: PIPE_LAUNCH(1, 0, 4, 2, false, false, true, true); break;
+    case LOFT_CONV_LEAN: PIPE_LAUNCH(1, 0, 4, 2, false, false, false, true); break;
+    case LOFT_CONV_XFIRST: PIPE_LAUNCH(1, 0, 4, 2, false, false, true); break;
+    case LOFT_CONV_W4: hipLaunchKernelGGL(conv_tap_w4_kernel<0>, grid, dim3(256), 0, s, a); break;
+    case LOFT_CONV_RING32: PIPE_LAUNCH(1, 0, 4, 2, false, true); break;
+    case LOFT_CONV_STREAM64N: PIPE_LAUNCH(1, 0, 1, 1); break;
+    case LOFT_CONV_STREAM256N: PIPE_LAUNCH(1, 0, 4, 1); break;
+    case LOFT_CONV_STREAM128: PIPE_LAUNCH(1, 0, 2); break;
+    case LOFT_CONV_STREAM64: PIPE_LAUNCH(1, 0, 1); break;
+    case LOFT_CONV_ROLES256: PIPE_LAUNCH(2, 0); break;
+    case LOFT_CONV_STREAM256:
+        if (n128) { PIPE_LAUNCH(1, 0, 4, 1); break; }
+        switch (p.var) {
         case 0: PIPE_LAUNCH(1, 0); break;
         case 1: PIPE_LAUNCH(1, 1); break;
         case 2: PIPE_LAUNCH(1, 2); break;      // direct (unstaged) epilogue
@@ -2056,8 +2024,9 @@ int loft_launch_conv_tap_pipe(const ConvArgs& a_in, int groups, int mode, int va
         case 15: PIPE_LAUNCH(1, 15); break;     // TRACE + halo-volume copies
         default: return (int)hipErrorInvalidValue;
         }
-    } else {
-        switch (var) {
+        break;
+    case LOFT_CONV_PIPE256:
+        switch (p.var) {
         case 0: PIPE_LAUNCH(0, 0); break;
         case 1: PIPE_LAUNCH(0, 1); break;
         case 4: PIPE_LAUNCH(0, 4); break;
@@ -2067,8 +2036,11 @@ int loft_launch_conv_tap_pipe(const ConvArgs& a_in, int groups, int mode, int va
         case 12: PIPE_LAUNCH(0, 12); break;
         default: return (int)hipErrorInvalidValue;
         }
+        break;
+    default: return (int)hipErrorInvalidValue;
     }
 #undef PIPE_LAUNCH
     LOFT_LAUNCH_CHECK();
     return 0;
 }
+

@@ -118,6 +118,72 @@ static inline void fastdiv_setup(unsigned d, unsigned* mul, unsigned* sh) {
     *sh = l;
 }
 
+// ---- host side of a launch: the shape as the C ABI hands it over, ONE builder for ConvArgs and the plan that conv_mfma.hip hands
+// to conv_pipe.hip.  (loft_conv_tap_bf16* / loft_deconv2x2_bf16 / loft_conv_tap_planes: include/loft_hip.h has the contract.)
+struct ConvShape {
+    int B, IH, IW, Cin, Cout, OH, OW, OHf, OWf, os, oo_y, oo_x, ss, T;
+    const int *dy, *dx, *wt;      // HOST tables, T entries each
+    int relu, out_f32, accumulate, groups;
+    long src_gs, wgt_gs, out_gs, bias_gs;
+};
+struct ConvOperands {
+    const void *src, *wgt;
+    const float* bias;
+    const void *residual, *mask;
+    void* out;
+    const void* zero_page;
+};
+
+// Row enumeration of a launch (ConvArgs::pixmajor, pm_S, pm_P) and its row count M.  THE rule for pixel-major rows in RoI blocks:
+// RoI maps (>= 256 maps of <= 1024 pixels, more than one tap, unit strides, a dense output) enumerate (position, RoI) so that taps
+// leaving the map are skipped per tile, in max(1, B / 256) blocks of S = ceil(B / blocks) >= 256 RoIs per position; rows of RoIs
+// >= B are padding: M = blocks * P * S >= P * B.  no_pixmajor (LOFT_CONV_FLAG_NO_PIXMAJOR, and every kernel without the mode)
+// switches it off, no_roi_blocks (LOFT_CONV_FLAG_NO_ROI_BLOCKS; the lockstep FAST kernel, which has no blocks) leaves ONE block.
+struct ConvRows { int pixmajor, S, P; long M; };
+static inline ConvRows conv_rows(const ConvShape& g, bool no_pixmajor, bool no_roi_blocks) {
+    ConvRows r{0, g.B, g.OH * g.OW, (long)g.B * g.OH * g.OW};
+    r.pixmajor = !no_pixmajor && g.T > 1 && g.T <= 32 && g.B >= 256 && g.OH * g.OW <= 1024 && g.os == 1 && g.ss == 1 &&
+                 g.OHf == g.OH && g.OWf == g.OW;
+    if (r.pixmajor) {
+        const int nb = no_roi_blocks ? 1 : g.B / 256;      // (B >= 256 here: at least one block)
+        r.S = (g.B + nb - 1) / nb;
+        r.M = (long)nb * r.P * r.S;
+    }
+    return r;
+}
+
+// What conv_mfma.hip decides about a launch (conv_tap_plan) and ALL it hands to conv_pipe.hip besides the arguments.
+struct ConvTapPlan {
+    int kernel;           // the LOFT_CONV_* code of the instance that launches: LOFT_CONV_AUTO and the process-wide stream form are
+                          // resolved (a STREAM256 launched under form 2 reads LOFT_CONV_LEAN); 0: no output pixel, nothing launches
+    int tile_m, tile_n;   // pixels (64 / 128 / 256) x couts (64 / 128 / 256) of a workgroup's tile
+    int var;              // experiment bits 12-15 of the variant (conv_pipe.hip VAR; PIPE256 and the 256 x 256 STREAM256 only)
+    ConvRows rows;
+    dim3 grid;
+};
+
+// Every field of ConvArgs a kernel of the family reads, from named inputs; what is not named here is ZERO (no head, no planes, no
+// par_n, chunk-major K order, no trace) and set by the one entry point that owns it.  conv_pipe.hip's launcher adds what depends
+// on the grid (gxy_*, gx_*, gy_*), pointwise and the packed tap tables.  rows.M > 0 (conv_tap_plan launches nothing otherwise).
+static inline ConvArgs conv_args_build(const ConvOperands& p, const ConvShape& g, const ConvRows& rows, int staged_out, int nfast) {
+    ConvArgs a{};
+    a.src = (const bf16_t*)p.src; a.wgt = (const bf16_t*)p.wgt; a.bias = p.bias; a.residual = (const bf16_t*)p.residual;
+    a.mask = (const bf16_t*)p.mask; a.out = p.out; a.zero_page = (const bf16_t*)p.zero_page;
+    a.B = g.B; a.IH = g.IH; a.IW = g.IW; a.Cin = g.Cin; a.Cout = g.Cout; a.OH = g.OH; a.OW = g.OW; a.OHf = g.OHf; a.OWf = g.OWf;
+    a.os = g.os; a.oo_y = g.oo_y; a.oo_x = g.oo_x; a.ss = g.ss; a.T = g.T;
+    for (int t = 0; t < g.T; ++t) { a.dy[t] = g.dy[t]; a.dx[t] = g.dx[t]; a.wt[t] = g.wt[t]; }
+    a.relu = g.relu; a.out_f32 = g.out_f32; a.accumulate = g.accumulate;
+    a.src_gs = g.src_gs; a.wgt_gs = g.wgt_gs; a.out_gs = g.out_gs; a.bias_gs = g.bias_gs;
+    a.staged_out = staged_out; a.nfast = nfast;
+    a.pixmajor = rows.pixmajor; a.pm_S = rows.S; a.pm_P = rows.P; a.M = (int)rows.M;
+    fastdiv_setup((unsigned)(g.OH * g.OW), &a.ohw_mul, &a.ohw_sh);
+    fastdiv_setup((unsigned)g.OW, &a.ow_mul, &a.ow_sh);
+    fastdiv_setup((unsigned)g.B, &a.b_mul, &a.b_sh);
+    fastdiv_setup((unsigned)a.pm_S, &a.pms_mul, &a.pms_sh);
+    fastdiv_setup((unsigned)a.pm_P, &a.pmp_mul, &a.pmp_sh);
+    return a;
+}
+
 __device__ __forceinline__ int swz(int row, int q) { return q ^ ((row >> 1) & 7); }
 
 // XCD-aware workgroup order (speed only, never correctness): hardware places linear workgroup L on XCD L % 8, each with

@@ -8,6 +8,7 @@ Layout contract: 4-D activations are NCHW-*shaped* tensors with channels_last st
 in memory (SURVEY.md section 8b "Tensor conventions"), so reference checkpoints and call sites
 keep their shapes while the kernels see channel-contiguous pixels.
 """
+import collections
 import ctypes
 import os
 
@@ -717,11 +718,14 @@ def conv_tap(src, wgt, out, B, IH, IW, Cin, Cout, OH, OW, OHf, OWf, taps, ss=1, 
     launch's epilogue when the library serves it (loft_conv_tap_bf16_head); head['fused'] tells the caller whether it did."""
     lib = L.load()
     L.dev_check(src, wgt, out, bias, residual)
+    T = len(taps)
+    dy = L.arr(c_int, [t[0] for t in taps])
+    dx = L.arr(c_int, [t[1] for t in taps])
+    wt = L.arr(c_int, [t[2] for t in taps])
     if src.dtype == torch.float32:
         for t in (wgt, out, residual, mask):
             if t is not None and t.dtype != torch.float32:
                 raise L.LoftHipError(f'fp32 parity mode needs every operand in fp32, got {t.dtype}')
-        T = len(taps)
         if (F32_CONTRACT in _PLANE_MODES and not accumulate and Cin % 64 == 0 and Cout % 128 == 0 and _dense(src) and _dense(wgt)
                 and src.numel() % 8 == 0 and wgt.numel() % 8 == 0 and B * OH * OW > 0):
             dt16, terms = _PLANE_MODES[F32_CONTRACT]
@@ -738,8 +742,7 @@ def conv_tap(src, wgt, out, B, IH, IW, Cin, Cout, OH, OW, OHf, OWf, taps, ss=1, 
                     _fwd_planes_put(src, dt16, (xp, ax))
                 e = plib.loft_conv_tap_planes(L.ptr(xp), L.ptr(wp), L.ptr(bias), L.ptr(residual), L.ptr(mask), L.ptr(out),
                                               L.ptr(zero_page(src.device)), B, IH, IW, Cin, Cout, OH, OW, OHf, OWf, os, oo[0], oo[1], ss, T,
-                                              L.arr(c_int, [t[0] for t in taps]), L.arr(c_int, [t[1] for t in taps]),
-                                              L.arr(c_int, [t[2] for t in taps]), int(relu), groups, src_gs, wgt_gs, out_gs, bias_gs,
+                                              dy, dx, wt, int(relu), groups, src_gs, wgt_gs, out_gs, bias_gs,
                                               len(terms), L.arr(c_int, [t[0] for t in terms]), L.arr(c_int, [t[1] for t in terms]),
                                               src.numel(), wgt.numel(), L.ptr(ax), L.ptr(aw), L.ptr(oslot), L.stream())
                 if e == 0:
@@ -753,17 +756,12 @@ def conv_tap(src, wgt, out, B, IH, IW, Cin, Cout, OH, OW, OHf, OWf, taps, ss=1, 
         _drop_amax(out)
         L.check(lib.loft_conv_tap_f32_v(L.ptr(src), L.ptr(wgt), L.ptr(bias), L.ptr(residual), L.ptr(mask), L.ptr(out),
                                         L.ptr(zero_page(src.device)), B, IH, IW, Cin, Cout, OH, OW, OHf, OWf, os, oo[0], oo[1], ss, T,
-                                        L.arr(c_int, [t[0] for t in taps]), L.arr(c_int, [t[1] for t in taps]),
-                                        L.arr(c_int, [t[2] for t in taps]), int(relu), int(accumulate), groups, src_gs, wgt_gs, out_gs,
+                                        dy, dx, wt, int(relu), int(accumulate), groups, src_gs, wgt_gs, out_gs,
                                         bias_gs, _f32_kernel_code(), L.stream()), 'loft_conv_tap_f32_v')
         return out
     _bf16(src), _bf16(wgt)
     if residual is not None:
         _bf16(residual)
-    T = len(taps)
-    dy = L.arr(c_int, [t[0] for t in taps])
-    dx = L.arr(c_int, [t[1] for t in taps])
-    wt = L.arr(c_int, [t[2] for t in taps])
     out_f32 = out.dtype == torch.float32
     if not out_f32:
         _bf16(out)
@@ -792,6 +790,29 @@ def conv_tap(src, wgt, out, B, IH, IW, Cin, Cout, OH, OW, OHf, OWf, taps, ss=1, 
                                      L.stream()), 'loft_conv_tap_bf16_v')
     _prof_end(_ev, 'conv_tap', 2.0 * groups * B * OH * OW * Cout * Cin * T, (groups, B, OH, OW, Cin, Cout, T, ss, os))
     return out
+
+
+ConvTapForm = collections.namedtuple('ConvTapForm', 'kernel tile_pixels tile_couts pixmajor rows')
+
+
+def conv_tap_form(B, IH, IW, Cin, Cout, OH, OW, OHf, OWf, taps, ss=1, os=1, oo=(0, 0), out_f32=False, accumulate=False, groups=1,
+                  variant=None, head_c4=0, residual=False, mask=False, nterms=0):
+    """The kernel conv_tap launches for 16-bit operands of this geometry (taps as there; variant: a CONV_* code with CONV_FLAG_*
+    bits, default the current CONV_VARIANT; head_c4: the launch with a narrow head of that many outputs; nterms > 0: the operand-
+    plane launch of the fp32 mode with that many terms) -> ConvTapForm(kernel = the CONV_* code of the instance that launches, AUTO
+    and the stream form resolved, 0 when there is no output pixel; tile pixels; tile couts; pixel-major rows; the rows enumerated,
+    with the padding of RoI blocks).  Asks the plan function of the launch path itself (loft_conv_tap_form); touches no device.
+    Raises LoftHipError where the launch returns hipErrorInvalidValue."""
+    lib = L.load()
+    T = len(taps)
+    if variant is None:
+        variant = CONV_VARIANT(groups, B, OH, OW, Cin, Cout, T, ss, os) if callable(CONV_VARIANT) else CONV_VARIANT
+    info = L.arr(c_int, [0] * 5)
+    L.check(lib.loft_conv_tap_form(B, IH, IW, Cin, Cout, OH, OW, OHf, OWf, os, oo[0], oo[1], ss, T, L.arr(c_int, [t[0] for t in taps]),
+                                   L.arr(c_int, [t[1] for t in taps]), L.arr(c_int, [t[2] for t in taps]), int(out_f32),
+                                   int(accumulate), groups, int(variant), head_c4, int(residual), int(mask), nterms, info),
+            'loft_conv_tap_form')
+    return ConvTapForm(info[0], info[1], info[2], bool(info[3]), info[4])
 
 
 def conv_out_size(i, k, stride, pad):

@@ -252,7 +252,10 @@ int loft_bneck_pair_bf16_v(const void* a_in, const void* w1, const float* bias1,
 #define LOFT_CONV_LEAN 18         /* the two-stage 256 x 256 stream schedule with fewer instructions per K-tile: compile-time chunk-major sequencer, one 64-bit scalar offset per K-tile, select-free activation copies on all-valid tiles (round 6; chunk-major launches only; bit-identical to LOFT_CONV_STREAM256) */
 #define LOFT_CONV_LEANX 19        /* LOFT_CONV_LEAN + LOFT_CONV_XFIRST */
 /* The form of the two-stage 256 x 256 stream schedule the dispatcher itself launches: 0 round 2's, 1 LOFT_CONV_XFIRST, 2 LOFT_CONV_LEAN,
- * 3 LOFT_CONV_LEANX (tap-major launches keep 0 / 1).  loft_conv_stream_form(form) sets it process-wide and returns the previous value
+ * 3 LOFT_CONV_LEANX.  It applies to every launch of LOFT_CONV_STREAM256's 256 x 256 tile without experiment bits, pinned or chosen.
+ * LOFT_CONV_LEAN is chunk-major only: a launch with LOFT_CONV_FLAG_TAP_MAJOR under form 2 or 3 falls back to form 0 (NOT to 1; under
+ * form 1 it takes LOFT_CONV_XFIRST); operand-plane launches take the lean instance under forms 2 and 3 and round 2's otherwise.
+ * loft_conv_stream_form(form) sets it process-wide and returns the previous value
  * (form < 0: query only) -- for same-box A/B runs of a whole step; results are bit-identical under every form.  form + 4: the
  * operand-plane launches of the 256 x 256 tile keep the direct fp32 epilogue instead of the LDS-staged one (round 6; bit-identical too). */
 #define LOFT_STREAM_FORM_DEFAULT 2
@@ -269,6 +272,21 @@ int loft_conv_tap_bf16_v(const void* src, const void* wgt, const float* bias, co
                          int OWf, int os, int oo_y, int oo_x, int ss, int T, const int* dy_host, const int* dx_host,
                          const int* wt_host, int relu, int out_f32, int accumulate, int groups, int64_t src_gs,
                          int64_t wgt_gs, int64_t out_gs, int64_t bias_gs, int variant, void* stream);
+/* Which kernel such a launch takes: the plan function the launches themselves call, without the launch -- no device is touched.
+ * The shape arguments and `variant` of loft_conv_tap_bf16_v; head_c4 > 0: the launch of loft_conv_tap_bf16_head with that head;
+ * residual / relu_mask != 0: the launch has that operand; nterms > 0: the launch of loft_conv_tap_planes with that many terms
+ * (variant LOFT_CONV_AUTO; out_f32 is implied).  -> 0 and form_out[0..4], or hipErrorInvalidValue (1) exactly when the launch
+ * returns it for these arguments:
+ *   form_out[0]  the LOFT_CONV_* code of the kernel that launches, LOFT_CONV_AUTO and the stream form resolved to the instance
+ *                (LOFT_CONV_STREAM256 under form 2 reads LOFT_CONV_LEAN); 0: no output pixel, nothing is launched
+ *   form_out[1]  pixels of a workgroup's tile (64 / 128 / 256; LOFT_CONV_PATCH64: its 16 x 16 patch)
+ *   form_out[2]  couts of the tile (64 / 128 / 256)
+ *   form_out[3]  1: rows enumerate (pixel position, RoI) -- the pixel-major mode of RoI maps
+ *   form_out[4]  the rows the launch enumerates: B * OH * OW, or with RoI blocks blocks * OH * OW * ceil(B / blocks)
+ * For tests: a shape written for one kernel must keep reaching it (tests/test_conv_tap_form_cpu.py). */
+int loft_conv_tap_form(int B, int IH, int IW, int Cin, int Cout, int OH, int OW, int OHf, int OWf, int os, int oo_y, int oo_x, int ss,
+                       int T, const int* dy_host, const int* dx_host, const int* wt_host, int out_f32, int accumulate, int groups,
+                       int variant, int head_c4, int residual, int relu_mask, int nterms, int* form_out);
 
 /* loft_conv_tap_bf16_head: loft_conv_tap_bf16 (one group, bf16 output, the library's own kernel choice) with a NARROW 1x1 HEAD on its
  * output computed in the epilogue, from the bf16 tile before it leaves LDS: head_out[pixel][n] = head_b[n] + sum_c bf16(out[pixel][c]) *

@@ -1,8 +1,9 @@
 """CPU: the table tests/test_conv_forms_gpu.py is parametrised over -- small ragged geometries of the forward / data-gradient
 tap convolution (loft_conv_tap_bf16_v), the 19 kernel codes with their order / layout flags and stream forms, the rule that says
-which kernel serves which launch (serves: the constraints include/loft_hip.h documents and conv_tap_bf16_impl /
-loft_launch_conv_tap_pipe enforce) -- and the reference: the defining sum of include/loft_hip.h written out in float64, checked
-here against F.conv2d, the autograd input gradient and F.conv_transpose2d."""
+which kernel serves which launch (serves: the constraints include/loft_hip.h documents and conv_refusal of csrc/conv_mfma.hip
+enforces; tests/test_conv_tap_form_cpu.py compares the two through loft_conv_tap_form, without a GPU) -- and the reference: the
+defining sum of include/loft_hip.h written out in float64, checked here against F.conv2d, the autograd input gradient and
+F.conv_transpose2d."""
 import collections
 
 import pytest
@@ -147,8 +148,8 @@ def cases_of(geo, epi):
 
 def serves(kernel, flags, geo, epi):
     """Whether loft_conv_tap_bf16_v launches `kernel` (a KERNELS name) with `flags` (CONV_FLAG_* names) on every launch of `geo`
-    with epilogue `epi`, or returns hipErrorInvalidValue -- from the constraints of include/loft_hip.h, conv_tap_bf16_impl and
-    loft_launch_conv_tap_pipe.  The answer is the same for all launches of a geometry (test_serves_is_one_answer_per_geometry)."""
+    with epilogue `epi`, or returns hipErrorInvalidValue -- from the constraints of include/loft_hip.h and conv_refusal
+    (csrc/conv_mfma.hip).  The answer is the same for all launches of a geometry (test_serves_is_one_answer_per_geometry)."""
     return all(_serves_launch(kernel, flags, geo, la, epi) for la in geo.launches)
 
 

@@ -1,7 +1,9 @@
 """GPU: every kernel of the forward / data-gradient tap convolution (loft_conv_tap_bf16_v: the 19 LOFT_CONV_* codes, their
 LOFT_CONV_FLAG_* order / layout flags, the process-wide stream forms, and whatever LOFT_CONV_AUTO picks) against the defining sum
 of include/loft_hip.h in float64, at the small ragged geometries of tests/test_conv_forms_cpu.py.  Nothing is skipped: a kernel
-that does not serve a launch (serves() of that file) must refuse it -- LoftHipError, the output untouched bit for bit.
+that does not serve a launch (serves() of that file) must refuse it -- LoftHipError, the output untouched bit for bit.  (That the
+library's conv_refusal / conv_tap_plan agree with serves(), and which kernel LOFT_CONV_AUTO takes for a shape, is checked without
+a GPU by tests/test_conv_tap_form_cpu.py.)
 
 The output is the middle of a larger allocation (one image in front, one behind) pre-filled with a pattern: after every launch the
 two guard images are the pattern still, and the positions outside the launch's parity class hold what they held.
