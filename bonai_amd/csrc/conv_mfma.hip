@@ -1584,229 +1584,269 @@ LOFT_EXPORT int loft_conv_wgrad_patch_bf16(const void* g, const void* x, float* 
 }
 
 
-// (conv_wgrad_pipe.hip; form_out != nullptr: *form_out = the LOFT_WGRAD_FORM_* code of the kernel they would launch, no launch)
-int loft_launch_conv_wgrad_stream(const WgradArgs& a, dim3 grid, bool pm, hipStream_t s, int* form_out);
-int loft_launch_conv_wgrad_ring(const WgradArgs& a, dim3 grid, hipStream_t s, int* form_out);
+// =====================================================================================
+// Host side of loft_conv_wgrad_bf16* / loft_conv_wgrad_planes: ONE decision, wgrad_plan, from host arithmetic alone -- no launch, no
+// device:  arguments valid (wgrad_validate) -> tile family (narrow / 128 / 256, lockstep / ring / stream) -> split-K factor
+// (wgrad_auto_splits) -> the valid-rows form of RoI maps with its tables (wgrad_pm_tables), or the row addressing of a dense map
+// (wgrad_row_form) -> form code, grid, slot count.  Every entry point calls plan -> wgrad_args_build (the ONLY place that fills a
+// WgradArgs, value-initialised) -> wgrad_launch and adds only what is its own; the plan is all conv_wgrad_pipe.hip gets besides the
+// arguments, and loft_conv_wgrad_slots / _form / _plan return fields of it without a launch.
+// A NEW FORM is registered in: its code in include/loft_hip.h, the line of wgrad_plan that chooses it, its template instance in
+// wgrad_launch (lockstep, narrow) or loft_launch_conv_wgrad_pipe (ring, stream), and its rows in tests/test_wgrad_forms_cpu.py.
+// =====================================================================================
+int loft_launch_conv_wgrad_pipe(const WgradArgs& a, const WgradPlan& p, hipStream_t s);     // conv_wgrad_pipe.hip
 
-// mode 0: launch, split-K combined with fp32 atomics into the zeroed dw.  mode 1: no launch, *nslots_out = the number of
-// split slots a partial-sum launch of this shape writes (0: this shape has no such form -- narrow channels, repeated or missing
-// weight taps, a tap without a valid row).  mode 2: launch, every workgroup STORES its tile into its split's slot of
-// dw = [group][nslots][T][Cout][Cin] (dw_gs = nslots * T * Cout * Cin); see WgradArgs::partial.  mode 3: mode 0's path up to the
-// launch, which is not made: *nslots_out = the LOFT_WGRAD_FORM_* code of the kernel mode 0 launches (loft_conv_wgrad_form).
-// Operand planes of a weight-gradient launch (loft_conv_wgrad_planes): the launch's groups are `groups * nterms` virtual groups,
-// virtual group grp * nterms + p reads G plane gpl[p] / X plane xpl[p] of real group grp and adds into that group's dW.
-struct WgradPlanes {
-    int nterms;
-    const int* gpl;
-    const int* xpl;
-    int64_t g_ps, x_ps;              // elements between two planes of G / X
-    const float* amax_g;
-    const float* amax_x;
-};
+static const int kInvalid = (int)hipErrorInvalidValue;
 
-static int wgrad_impl(const void* g, const void* x, float* dw, const void* zero_page, int B, int GH,
-                      int GW, int Cout, int XH, int XW, int Cin, int OH, int OW, int gos, int ss, int T,
-                      const int* goy_host, const int* gox_host, const int* dy_host, const int* dx_host,
-                      const int* wt_host, int groups, int64_t g_gs, int64_t x_gs, int64_t dw_gs,
-                      int splits, float* db, int db_tap, int variant, void* stream, int mode, int* nslots_out,
-                      const WgradPlanes* planes = nullptr) {
-    if (T < 1 || T > CONV_MAX_TAPS || (Cin % 8) || (Cout % 8) || groups < 1) return (int)hipErrorInvalidValue;
-    if (variant < LOFT_WGRAD_AUTO || variant > LOFT_WGRAD_RING128) return (int)hipErrorInvalidValue;
-    const bool narrow = (Cin % 128) || (Cout % 128);
-    bool slots_ok = !narrow;
-    {   // every weight tap written by exactly one tap of the table (else a slot would be written twice, or never)
-        unsigned seen = 0;
-        for (int t = 0; t < T; ++t) {
-            if (wt_host[t] < 0 || wt_host[t] >= T || (seen >> wt_host[t] & 1u)) slots_ok = false;
-            else seen |= 1u << wt_host[t];
-        }
-    }
-    if (nslots_out) *nslots_out = 0;
-    int* const form_out = mode == 3 ? nslots_out : nullptr;      // mode 3: the out parameter carries the form code, ...
-    static_assert(LOFT_WGRAD_FORM_NONE == 0, "... and the zero stored above must read as 'nothing is launched'");
-    if (mode == 2 && !slots_ok) return (int)hipErrorInvalidValue;
-    WgradArgs a;
-    a.pm_inc_ok = 0;
-    a.nvg = 0; a.amax_g = nullptr; a.amax_x = nullptr;
-    if (planes) {
-        if (mode != 0 || planes->nterms < 1 || planes->nterms > CONV_MAX_TERMS || groups * planes->nterms > WGRAD_MAX_VGROUPS)
-            return (int)hipErrorInvalidValue;
-        if (db) {
+// THE map-size predicate of the decode-free row addressing (and of the ring's split target): unit strides, G / X / output maps of
+// one size.
+static bool wgrad_same_size(const WgradShape& g) {
+    return g.gos == 1 && g.ss == 1 && g.GH == g.OH && g.GW == g.OW && g.XH == g.OH && g.XW == g.OW;
+}
+
+// Row addressing of a launch that is not PM.  DENSE: one tap at offset zero on maps of one size (reduction row m is pixel m of both
+// operands); SAME: maps of one size, taps offset on the X side only, rows of at least min_ow pixels (a K-step wraps at most one
+// row: 32 for the ring's 32-pixel steps, 64 for the stream and the narrow kernel); GENERIC: the per-row decode.
+enum { WGRAD_ROWS_GENERIC = 0, WGRAD_ROWS_DENSE = 1, WGRAD_ROWS_SAME = 2 };
+static int wgrad_row_form(const WgradShape& g, int min_ow) {
+    bool g_at_zero = wgrad_same_size(g);
+    for (int t = 0; t < g.T; ++t) g_at_zero = g_at_zero && g.goy[t] == 0 && g.gox[t] == 0;
+    if (!g_at_zero) return WGRAD_ROWS_GENERIC;
+    if (g.T == 1 && g.dy[0] == 0 && g.dx[0] == 0) return WGRAD_ROWS_DENSE;
+    return g.OW >= min_ow ? WGRAD_ROWS_SAME : WGRAD_ROWS_GENERIC;
+}
+
+// What every launch and every query of the family rejects, in one place.  (A launch without a pixel is no launch whatever its
+// variant: the variant is held against the channel counts only when there is one.)
+static int wgrad_validate(const WgradShape& g, const WgradAsk& q) {
+    if (g.T < 1 || g.T > CONV_MAX_TAPS || (g.Cin % 8) || (g.Cout % 8) || g.groups < 1) return kInvalid;
+    if (q.variant < LOFT_WGRAD_AUTO || q.variant > LOFT_WGRAD_RING128) return kInvalid;
+    const bool narrow = (g.Cin % 128) || (g.Cout % 128);
+    if (q.nterms) {      // operand planes: wide channels, the atomics launch only, groups x terms virtual groups
+        if (narrow || q.want_slots || q.nterms < 1 || q.nterms > CONV_MAX_TERMS || g.groups * q.nterms > WGRAD_MAX_VGROUPS) return kInvalid;
+        if (q.has_db && q.gpl) {
             // the bias gradient of a plane launch = the column sums of ALL planes of G: every G plane that occurs in a term must be
             // paired with X plane 0 in exactly one term -- that term's workgroups carry its sum (true of the three term lists)
             unsigned seen = 0u, want = 0u;
-            for (int p = 0; p < planes->nterms; ++p) {
-                if (planes->gpl[p] < 0 || planes->gpl[p] > 31) return (int)hipErrorInvalidValue;
-                want |= 1u << planes->gpl[p];
-                if (planes->xpl[p] == 0) {
-                    if (seen >> planes->gpl[p] & 1u) return (int)hipErrorInvalidValue;
-                    seen |= 1u << planes->gpl[p];
+            for (int p = 0; p < q.nterms; ++p) {
+                if (q.gpl[p] < 0 || q.gpl[p] > 31) return kInvalid;
+                want |= 1u << q.gpl[p];
+                if (q.xpl[p] == 0) {
+                    if (seen >> q.gpl[p] & 1u) return kInvalid;
+                    seen |= 1u << q.gpl[p];
                 }
             }
-            if (seen != want) return (int)hipErrorInvalidValue;
+            if (seen != want) return kInvalid;
         }
-        a.nvg = groups * planes->nterms;
-        for (int gr = 0; gr < groups; ++gr)
-            for (int p = 0; p < planes->nterms; ++p) {
-                const int v = gr * planes->nterms + p;
-                a.vg_g[v] = (long)gr * g_gs + (long)planes->gpl[p] * planes->g_ps;
-                a.vg_x[v] = (long)gr * x_gs + (long)planes->xpl[p] * planes->x_ps;
-                a.vg_dw[v] = (long)gr * dw_gs;
-                a.vg_db[v] = (db && planes->xpl[p] == 0) ? gr * Cout : -1;
-            }
-        a.amax_g = planes->amax_g; a.amax_x = planes->amax_x;
-        groups = a.nvg;                       // from here on: launch geometry and split counts over the virtual groups
     }
-    a.partial = mode == 2; a.nslots = 1; a.split_stride = (long)T * Cout * Cin;
-    a.g = (const bf16_t*)g; a.x = (const bf16_t*)x; a.dw = dw; a.zero_page = (const bf16_t*)zero_page;
-    a.B = B; a.GH = GH; a.GW = GW; a.Cout = Cout; a.XH = XH; a.XW = XW; a.Cin = Cin; a.OH = OH; a.OW = OW;
-    a.gos = gos; a.ss = ss; a.T = T;
+    const long M = (long)g.B * g.OH * g.OW;
+    if (M > 0x7fffffffL) return kInvalid;
+    if (M > 0) {
+        const bool big_ok = (g.Cout % 256 == 0) && (g.Cin % 256 == 0);
+        if ((q.variant == LOFT_WGRAD_STREAM256 || q.variant == LOFT_WGRAD_T256) && !big_ok) return kInvalid;
+        if ((q.variant == LOFT_WGRAD_T128 || q.variant == LOFT_WGRAD_RING128) && narrow) return kInvalid;
+    }
+    return 0;
+}
+
+// The library's split-K factor (splits <= 0) for `tiles` channel tiles per tap and group: ~512 workgroups (two resident 128-tile
+// workgroups per CU).  More splits only add fp32 atomic traffic to dW -- measured on the 1x1 shapes: 1024 workgroups 202-222
+// TFLOP/s, 512: 279-305, 256: 261-274.
+// (the four-stage ring kernel with its decode-free row addressing: ~288 workgroups are best on every backbone shape,
+//  tools/probes/wgrad_splits.py -- layer3 1x1 37.6 us at 256 against 46 at 512, layer3 3x3 78 at 288 against 91 / 99)
+// (big tile, one workgroup per CU; measured: 256 workgroups 708-791 TFLOP/s on the FOA / mask / P2-P3 3x3 shapes, 512: 606-754,
+//  1024: 474-719)
+// (also measured: a single-stage 128-tile form at four workgroups per CU -- what helped the K-shallow forward convs -- changes
+//  nothing here, with 512 or 1024 workgroups: these launches are bound by the fp32-atomic epilogue and the operand re-reads, not
+//  by the per-K-step round trip)
+static int wgrad_auto_splits(const WgradShape& g, int variant, bool narrow, bool big, long tiles, int vgroups, long M) {
+    const bool ring = !narrow && variant != LOFT_WGRAD_T128 && wgrad_same_size(g);
+    const long target = big ? 256 : ring ? 288 : 512;
+    const long want = target / (tiles * g.T * vgroups), maxs = (M + 255) / 256;
+    return (int)(want < 1 ? 1 : (want > maxs ? maxs : want));
+}
+
+// The tables of the PM form (WgradArgs documents them) for a workgroup budget per group and channel tile: the valid rectangle of
+// every tap, and K-splits over RoI ranges (split s of tap t = RoIs [s * rb_t, (s + 1) * rb_t) at all of the tap's positions) with
+// rb_t chosen per tap for a common K length: the smallest L (rows per split, a multiple of the 64-row K-step) with
+// sum_t ceil(B / floor(L / positions_t)) <= budget.  -> the blocks (workgroups) of all taps together, 0: no tap has a valid row;
+// *nslots = the splits of the tap that has the most; *every = every tap has a split.
+static int wgrad_pm_tables(const WgradShape& g, long budget, WgradPmTables* pt, int* nslots, bool* every) {
+    const int T = g.T, B = g.B;
+    long npos[CONV_MAX_TAPS], total = 0;
     for (int t = 0; t < T; ++t) {
-        a.goy[t] = goy_host[t]; a.gox[t] = gox_host[t]; a.dy[t] = dy_host[t]; a.dx[t] = dx_host[t]; a.wt[t] = wt_host[t];
+        const int ylo = std::max(0, std::max(-g.goy[t], -g.dy[t])), yhi = std::min(g.OH, std::min(g.GH - g.goy[t], g.XH - g.dy[t]));
+        const int xlo = std::max(0, std::max(-g.gox[t], -g.dx[t])), xhi = std::min(g.OW, std::min(g.GW - g.gox[t], g.XW - g.dx[t]));
+        const int rh = std::max(0, yhi - ylo), rw = std::max(0, xhi - xlo);
+        pt->y0[t] = ylo; pt->x0[t] = xlo; pt->rw[t] = rw > 0 ? rw : 1;
+        fastdiv_setup((unsigned)pt->rw[t], &pt->rw_mul[t], &pt->rw_sh[t]);
+        npos[t] = (long)rh * rw;
+        total += npos[t] * B;
     }
-    a.g_gs = g_gs; a.x_gs = x_gs; a.dw_gs = dw_gs;
-    a.db = db; a.db_tap = db ? db_tap : -1;
-    const long M = (long)B * OH * OW;
-    if (M <= 0) return mode == 2 ? (int)hipErrorInvalidValue : 0;          // (mode 3: LOFT_WGRAD_FORM_NONE, set above)
-    if (M > 0x7fffffffL) return (int)hipErrorInvalidValue;
-    a.M = (int)M;
-    fastdiv_setup((unsigned)(OH * OW), &a.ohw_mul, &a.ohw_sh);
-    fastdiv_setup((unsigned)OW, &a.ow_mul, &a.ow_sh);
-    // 256x256 tiles only when >= 256 workgroups can each run >= ~32 K-steps (else the 65k-atomic epilogue dominates)
-    const bool big_ok = (Cout % 256 == 0) && (Cin % 256 == 0);
-    if ((variant == LOFT_WGRAD_STREAM256 || variant == LOFT_WGRAD_T256) && !big_ok) return (int)hipErrorInvalidValue;
-    if ((variant == LOFT_WGRAD_T128 || variant == LOFT_WGRAD_RING128) && narrow) return (int)hipErrorInvalidValue;
-    const bool big = variant == LOFT_WGRAD_AUTO ? (big_ok && M * (long)(Cout / 256) * (Cin / 256) * T * groups >= 524288L)
-                                                : (variant != LOFT_WGRAD_T128 && variant != LOFT_WGRAD_RING128);
-    const bool piped = big && variant != LOFT_WGRAD_T256;       // the software-pipelined form (conv_wgrad_pipe.hip)
-    const int TNv = narrow ? 64 : (big ? 256 : 128);
-    a.ctiles = (Cin + TNv - 1) / TNv;
-    const int tiles = ((Cout + TNv - 1) / TNv) * a.ctiles;
-    if (splits <= 0) {
-        // split-K factor: ~512 workgroups (two resident 128-tile workgroups per CU).  More splits only add fp32 atomic
-        // traffic to dW -- measured on the 1x1 shapes: 1024 workgroups 202-222 TFLOP/s, 512: 279-305, 256: 261-274.
-        // (the four-stage ring kernel with its decode-free row addressing: ~288 workgroups are best on every backbone shape,
-        //  tools/probes/wgrad_splits.py -- layer3 1x1 37.6 us at 256 against 46 at 512, layer3 3x3 78 at 288 against 91 / 99)
-        const bool ring = !narrow && variant != LOFT_WGRAD_T128 && gos == 1 && ss == 1 && GH == OH && GW == OW && XH == OH && XW == OW;
-        const long tgt_small = ring ? 288 : 512;
-        const long tgt_big = 256;   // 256-tile: one workgroup per CU
-        // (big tile, measured: 256 workgroups 708-791 TFLOP/s on the FOA / mask / P2-P3 3x3 shapes, 512: 606-754, 1024: 474-719)
-        // (also measured: a single-stage 128-tile form at four workgroups per CU -- what helped the K-shallow forward convs --
-        //  changes nothing here, with 512 or 1024 workgroups: these launches are bound by the fp32-atomic epilogue and the
-        //  operand re-reads, not by the per-K-step round trip)
-        long want = (big ? tgt_big : tgt_small) / ((long)tiles * T * groups);
-        long maxs = (M + 255) / 256;
-        splits = (int)(want < 1 ? 1 : (want > maxs ? maxs : want));
+    if (total <= 0) return 0;
+    long L = ((total + budget - 1) / budget + 63) / 64 * 64;
+    for (;; L += 64) {
+        long nb = 0;
+        for (int t = 0; t < T; ++t)
+            if (npos[t] > 0) {
+                const long rb = std::max<long>(1, L / npos[t]);
+                nb += (B + rb - 1) / rb;
+            }
+        if (nb <= budget) break;
     }
-    int pps = (int)((M + splits - 1) / splits);
-    pps = ((pps + 63) / 64) * 64;
-    a.pix_per_split = pps;
-    if (!narrow && T > 1 && gos == 1 && ss == 1 && B >= 128 && OH * OW <= 1024) {
-        // valid rectangle of every tap; K-splits over RoI ranges (WgradArgs: split s of tap t = RoIs [s * rb_t, (s + 1) * rb_t) at all
-        // of the tap's positions), rb_t chosen per tap for a common K length: the smallest L (rows per split, multiple of the
-        // 64-row K-step) with sum_t ceil(B / floor(L / positions_t)) <= the workgroup budget per group
-        const long budget = std::min<long>((long)splits * T, WGRAD_PM_MAX_BLOCKS);    // (pm_tap / pm_split hold one byte per block)
-        long npos[CONV_MAX_TAPS], total = 0;
+    int blk = 0, ns[CONV_MAX_TAPS], nxt[CONV_MAX_TAPS];
+    *nslots = 0; *every = true;
+    for (int t = 0; t < T; ++t) {
+        long rb = 1;
+        ns[t] = 0; nxt[t] = 0;
+        if (npos[t] > 0) {
+            rb = std::max<long>(1, L / npos[t]);
+            ns[t] = (int)((B + rb - 1) / rb);
+            rb = (B + ns[t] - 1) / ns[t];                     // same number of splits, evenly sized RoI ranges
+        }
+        pt->blk0[t] = blk;
+        pt->pps[t] = (int)rb;
+        pt->rows[t] = (int)(npos[t] * rb);
+        fastdiv_setup((unsigned)rb, &pt->pps_mul[t], &pt->pps_sh[t]);
+        blk += ns[t];
+        *nslots = std::max(*nslots, ns[t]);
+        *every = *every && ns[t] >= 1;
+    }
+    pt->blk0[T] = blk;
+    if (blk > WGRAD_PM_MAX_BLOCKS) return blk;               // (pm_tap / pm_split hold one byte per block; the caller rejects it)
+    // interleave the taps: sort (tap, split) by the split's relative position (s + 0.5) / ns_t, ties by tap
+    for (int j = 0; j < blk; ++j) {
+        int best = -1;
         for (int t = 0; t < T; ++t) {
-            const int ylo = std::max(0, std::max(-a.goy[t], -a.dy[t])), yhi = std::min(OH, std::min(GH - a.goy[t], XH - a.dy[t]));
-            const int xlo = std::max(0, std::max(-a.gox[t], -a.dx[t])), xhi = std::min(OW, std::min(GW - a.gox[t], XW - a.dx[t]));
-            const int rh = std::max(0, yhi - ylo), rw = std::max(0, xhi - xlo);
-            a.pm_y0[t] = ylo; a.pm_x0[t] = xlo; a.pm_rw[t] = rw > 0 ? rw : 1;
-            fastdiv_setup((unsigned)a.pm_rw[t], &a.pm_rw_mul[t], &a.pm_rw_sh[t]);
-            npos[t] = (long)rh * rw;
-            total += npos[t] * B;
+            if (nxt[t] >= ns[t]) continue;
+            // (2 nxt + 1) / (2 ns) compared by cross-multiplication
+            if (best < 0 || (long)(2 * nxt[t] + 1) * ns[best] < (long)(2 * nxt[best] + 1) * ns[t]) best = t;
         }
-        if (total > 0) {
-            long L = ((total + budget - 1) / budget + 63) / 64 * 64;
-            for (;; L += 64) {
-                long nb = 0;
-                for (int t = 0; t < T; ++t)
-                    if (npos[t] > 0) {
-                        const long rb = std::max<long>(1, L / npos[t]);
-                        nb += (B + rb - 1) / rb;
-                    }
-                if (nb <= budget) break;
-            }
-            int blk = 0;
-            for (int t = 0; t < T; ++t) {
-                long ns = 0, rb = 1;
-                if (npos[t] > 0) {
-                    rb = std::max<long>(1, L / npos[t]);
-                    ns = (B + rb - 1) / rb;
-                    rb = (B + ns - 1) / ns;                      // same number of splits, evenly sized RoI ranges
-                }
-                a.pm_blk0[t] = blk;
-                a.pm_pps[t] = (int)rb;
-                a.pm_rows[t] = (int)(npos[t] * rb);
-                fastdiv_setup((unsigned)rb, &a.pm_pps_mul[t], &a.pm_pps_sh[t]);
-                blk += (int)ns;
-            }
-            a.pm_blk0[T] = blk;
-            if (blk > WGRAD_PM_MAX_BLOCKS) return (int)hipErrorInvalidValue;      // (budget = 256 / (tiles * groups) at most)
-            {   // interleave the taps: sort (tap, split) by the split's relative position (s + 0.5) / ns_t, ties by tap
-                int ns[CONV_MAX_TAPS], nxt[CONV_MAX_TAPS];
-                for (int t = 0; t < T; ++t) { ns[t] = a.pm_blk0[t + 1] - a.pm_blk0[t]; nxt[t] = 0; }
-                for (int j = 0; j < blk; ++j) {
-                    int best = -1;
-                    for (int t = 0; t < T; ++t) {
-                        if (nxt[t] >= ns[t]) continue;
-                        // (2 nxt + 1) / (2 ns) compared by cross-multiplication
-                        if (best < 0 || (long)(2 * nxt[t] + 1) * ns[best] < (long)(2 * nxt[best] + 1) * ns[t]) best = t;
-                    }
-                    a.pm_tap[j] = (unsigned char)best;
-                    a.pm_split[j] = (unsigned char)nxt[best]++;
-                }
-            }
-            fastdiv_setup((unsigned)B, &a.b_mul, &a.b_sh);
-            a.pm_inc_ok = ((long)groups * B * GH * GW * Cout < 0x7fffffffL && (long)groups * B * XH * XW * Cin < 0x7fffffffL) ? 1 : 0;
-            int maxns = 0;
-            bool every = true;
-            for (int t = 0; t < T; ++t) {
-                const int ns = a.pm_blk0[t + 1] - a.pm_blk0[t];
-                maxns = std::max(maxns, ns);
-                every = every && ns >= 1;
-            }
-            a.nslots = maxns;
-            if (mode == 1) { if (nslots_out) *nslots_out = (slots_ok && every) ? maxns : 0; return 0; }
-            if (mode == 2 && (!every || dw_gs != (int64_t)maxns * a.split_stride)) return (int)hipErrorInvalidValue;
-            dim3 grid(tiles, groups, blk);
-            if (piped) return loft_launch_conv_wgrad_stream(a, grid, true, (hipStream_t)stream, form_out);
-            const int form = big ? LOFT_WGRAD_FORM_T256_PM : LOFT_WGRAD_FORM_T128_PM;
-            if (form_out) { *form_out = form; return 0; }
-            if (form == LOFT_WGRAD_FORM_T256_PM) hipLaunchKernelGGL((conv_wgrad_kernel<256, 8, true>), grid, dim3(512), 0, (hipStream_t)stream, a);
-            else hipLaunchKernelGGL((conv_wgrad_kernel<128, 4, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
-            LOFT_LAUNCH_CHECK();
-            return 0;
+        pt->tap[j] = (unsigned char)best;
+        pt->split[j] = (unsigned char)nxt[best]++;
+    }
+    fastdiv_setup((unsigned)B, &pt->b_mul, &pt->b_sh);
+    return blk;
+}
+
+// Shape + ask -> plan.  -> 0 and *out (form NONE: nothing to launch -- no pixel, or no tap of a RoI map has a valid row), or
+// hipErrorInvalidValue: arguments no launch takes, or a slot launch asked of a shape that has none.
+static int wgrad_plan(const WgradShape& g, const WgradAsk& q, WgradPlan* out) {
+    WgradPlan p{};
+    p.grid = dim3(0, 0, 0);
+    *out = p;
+    if (const int e = wgrad_validate(g, q)) return e;
+    const bool narrow = (g.Cin % 128) || (g.Cout % 128);
+    p.slots_ok = !narrow;
+    unsigned seen = 0;       // every weight tap written by exactly one tap of the table (else a slot would be written twice, or never)
+    for (int t = 0; t < g.T; ++t) {
+        if (g.wt[t] < 0 || g.wt[t] >= g.T || (seen >> g.wt[t] & 1u)) p.slots_ok = false;
+        else seen |= 1u << g.wt[t];
+    }
+    const long M = (long)g.B * g.OH * g.OW;
+    if (q.want_slots && (!p.slots_ok || M <= 0)) return kInvalid;
+    if (M <= 0) return 0;
+    p.vgroups = g.groups * std::max(1, q.nterms);     // launch geometry and split counts run over the virtual groups
+    // 256x256 tiles only when >= 256 workgroups can each run >= ~32 K-steps (else the 65k-atomic epilogue dominates)
+    const bool big = q.variant == LOFT_WGRAD_AUTO
+        ? (g.Cout % 256 == 0 && g.Cin % 256 == 0 && M * (long)(g.Cout / 256) * (g.Cin / 256) * g.T * p.vgroups >= 524288L)
+        : (q.variant != LOFT_WGRAD_T128 && q.variant != LOFT_WGRAD_RING128);
+    const bool stream = big && q.variant != LOFT_WGRAD_T256;                  // the software-pipelined form (conv_wgrad_pipe.hip)
+    const bool ring = !narrow && !big && q.variant != LOFT_WGRAD_T128;        // four-stage ring (conv_wgrad_pipe.hip)
+    p.tile = narrow ? 64 : (big ? 256 : 128);
+    p.threads = big ? 512 : 256;
+    p.ctiles = loft_cdiv(g.Cin, p.tile);
+    const int tiles = loft_cdiv(g.Cout, p.tile) * p.ctiles;
+    p.splits = q.splits > 0 ? q.splits : wgrad_auto_splits(g, q.variant, narrow, big, tiles, p.vgroups, M);
+    p.pix_per_split = (loft_cdiv(M, p.splits) + 63) / 64 * 64;
+    p.pm = !narrow && g.T > 1 && g.gos == 1 && g.ss == 1 && g.B >= 128 && g.OH * g.OW <= 1024;
+    if (p.pm) {
+        bool every = true;
+        const int blk = wgrad_pm_tables(g, std::min<long>((long)p.splits * g.T, WGRAD_PM_MAX_BLOCKS), &p.pmt, &p.nslots, &every);
+        if (blk > WGRAD_PM_MAX_BLOCKS) return kInvalid;      // (budget = 256 / (tiles * groups) at most)
+        if (blk == 0) return q.want_slots ? kInvalid : 0;    // (no tap has a valid row: dw stays as the caller left it)
+        p.slots_ok = p.slots_ok && every;
+        if (q.want_slots && !every) return kInvalid;
+        p.pm_inc_ok = ((long)p.vgroups * g.B * g.GH * g.GW * g.Cout < 0x7fffffffL && (long)p.vgroups * g.B * g.XH * g.XW * g.Cin < 0x7fffffffL) ? 1 : 0;
+        bool inc = p.pm_inc_ok;                              // stream: the incremental decode needs >= 64 RoIs in every split
+        for (int t = 0; t < g.T && inc; ++t) inc = p.pmt.blk0[t + 1] == p.pmt.blk0[t] || p.pmt.pps[t] >= 64;
+        p.form = stream ? (inc ? LOFT_WGRAD_FORM_STREAM_PM_INC : LOFT_WGRAD_FORM_STREAM_PM)
+                        : (big ? LOFT_WGRAD_FORM_T256_PM : LOFT_WGRAD_FORM_T128_PM);
+        p.grid = dim3(tiles, p.vgroups, blk);
+    } else {
+        static const int kNarrow[3] = {LOFT_WGRAD_FORM_NARROW_GENERIC, LOFT_WGRAD_FORM_NARROW_DENSE, LOFT_WGRAD_FORM_NARROW_SAME};
+        static const int kRing[3] = {LOFT_WGRAD_FORM_RING_GENERIC, LOFT_WGRAD_FORM_RING_DENSE, LOFT_WGRAD_FORM_RING_SAME};
+        static const int kStream[3] = {LOFT_WGRAD_FORM_STREAM_GENERIC, LOFT_WGRAD_FORM_STREAM_DENSE, LOFT_WGRAD_FORM_STREAM_SAME};
+        p.splits = p.nslots = loft_cdiv(M, p.pix_per_split);       // (recomputed from the rounded split length)
+        p.form = narrow ? kNarrow[wgrad_row_form(g, 64)] : stream ? kStream[wgrad_row_form(g, 64)] : ring ? kRing[wgrad_row_form(g, 32)]
+                 : (big ? LOFT_WGRAD_FORM_T256 : LOFT_WGRAD_FORM_T128);
+        p.grid = dim3(tiles, g.T * p.vgroups, p.splits);
+    }
+    *out = p;
+    return 0;
+}
+
+// Every field of WgradArgs a kernel of the family reads, from named inputs: operands (with their group strides, the optional db
+// and operand planes), shape, plan; what is not named here is ZERO.  partial: WgradArgs::partial (loft_conv_wgrad_bf16_slots).
+static WgradArgs wgrad_args_build(const WgradOperands& o, const WgradShape& g, const WgradPlan& p, int partial) {
+    WgradArgs a{};
+    a.g = (const bf16_t*)o.g; a.x = (const bf16_t*)o.x; a.dw = o.dw; a.zero_page = (const bf16_t*)o.zero_page;
+    a.B = g.B; a.GH = g.GH; a.GW = g.GW; a.Cout = g.Cout; a.XH = g.XH; a.XW = g.XW; a.Cin = g.Cin; a.OH = g.OH; a.OW = g.OW;
+    a.gos = g.gos; a.ss = g.ss; a.T = g.T;
+    for (int t = 0; t < g.T; ++t) { a.goy[t] = g.goy[t]; a.gox[t] = g.gox[t]; a.dy[t] = g.dy[t]; a.dx[t] = g.dx[t]; a.wt[t] = g.wt[t]; }
+    a.g_gs = o.g_gs; a.x_gs = o.x_gs; a.dw_gs = o.dw_gs;
+    a.db = o.db; a.db_tap = o.db ? o.db_tap : -1;
+    a.M = g.B * g.OH * g.OW; a.pix_per_split = p.pix_per_split; a.ctiles = p.ctiles;
+    fastdiv_setup((unsigned)(g.OH * g.OW), &a.ohw_mul, &a.ohw_sh);
+    fastdiv_setup((unsigned)g.OW, &a.ow_mul, &a.ow_sh);
+    a.partial = partial; a.nslots = p.nslots; a.split_stride = (long)g.T * g.Cout * g.Cin;
+    if (p.pm) {
+        const WgradPmTables& pt = p.pmt;
+        std::copy(pt.blk0, pt.blk0 + CONV_MAX_TAPS + 1, a.pm_blk0);
+        std::copy(pt.pps, pt.pps + CONV_MAX_TAPS, a.pm_pps); std::copy(pt.rows, pt.rows + CONV_MAX_TAPS, a.pm_rows);
+        std::copy(pt.pps_mul, pt.pps_mul + CONV_MAX_TAPS, a.pm_pps_mul); std::copy(pt.pps_sh, pt.pps_sh + CONV_MAX_TAPS, a.pm_pps_sh);
+        std::copy(pt.tap, pt.tap + WGRAD_PM_MAX_BLOCKS, a.pm_tap); std::copy(pt.split, pt.split + WGRAD_PM_MAX_BLOCKS, a.pm_split);
+        std::copy(pt.y0, pt.y0 + CONV_MAX_TAPS, a.pm_y0); std::copy(pt.x0, pt.x0 + CONV_MAX_TAPS, a.pm_x0);
+        std::copy(pt.rw, pt.rw + CONV_MAX_TAPS, a.pm_rw);
+        std::copy(pt.rw_mul, pt.rw_mul + CONV_MAX_TAPS, a.pm_rw_mul); std::copy(pt.rw_sh, pt.rw_sh + CONV_MAX_TAPS, a.pm_rw_sh);
+        a.b_mul = pt.b_mul; a.b_sh = pt.b_sh;
+        a.pm_inc_ok = p.pm_inc_ok;
+    }
+    if (const WgradPlanes* pl = o.planes) {           // virtual group gr * nterms + t: term t of real group gr
+        a.nvg = g.groups * pl->nterms;
+        for (int v = 0; v < a.nvg; ++v) {
+            const int gr = v / pl->nterms, t = v % pl->nterms;
+            a.vg_g[v] = (long)gr * o.g_gs + (long)pl->gpl[t] * pl->g_ps;
+            a.vg_x[v] = (long)gr * o.x_gs + (long)pl->xpl[t] * pl->x_ps;
+            a.vg_dw[v] = (long)gr * o.dw_gs;
+            a.vg_db[v] = (o.db && pl->xpl[t] == 0) ? gr * g.Cout : -1;
         }
-        return mode == 2 ? (int)hipErrorInvalidValue : 0;     // (no tap has a valid row: dw stays as the caller left it)
+        a.amax_g = pl->amax_g; a.amax_x = pl->amax_x;
     }
-    splits = (int)((M + pps - 1) / pps);
-    a.nslots = splits;
-    if (mode == 1) { if (nslots_out) *nslots_out = slots_ok ? splits : 0; return 0; }
-    if (mode == 2 && dw_gs != (int64_t)splits * a.split_stride) return (int)hipErrorInvalidValue;
-    dim3 grid(tiles, T * groups, splits);
-    if (piped) return loft_launch_conv_wgrad_stream(a, grid, false, (hipStream_t)stream, form_out);
-    if (narrow) {
-        const bool samesize = gos == 1 && ss == 1 && GH == OH && GW == OW && XH == OH && XW == OW;
-        bool same = samesize && OW >= 64;
-        for (int t = 0; t < T; ++t) same = same && a.goy[t] == 0 && a.gox[t] == 0;
-        const bool dense = samesize && T == 1 && a.goy[0] == 0 && a.gox[0] == 0 && a.dy[0] == 0 && a.dx[0] == 0;
-        const int form = dense ? LOFT_WGRAD_FORM_NARROW_DENSE : same ? LOFT_WGRAD_FORM_NARROW_SAME : LOFT_WGRAD_FORM_NARROW_GENERIC;
-        if (form_out) { *form_out = form; return 0; }
-        if (form == LOFT_WGRAD_FORM_NARROW_DENSE) hipLaunchKernelGGL(conv_wgrad64_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, a);
-        else if (form == LOFT_WGRAD_FORM_NARROW_SAME) hipLaunchKernelGGL(conv_wgrad64_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL(conv_wgrad64_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, a);
-    }
-    else if (!big && variant != LOFT_WGRAD_T128)
-        return loft_launch_conv_wgrad_ring(a, grid, (hipStream_t)stream, form_out);          // four-stage ring (conv_wgrad_pipe.hip)
-    else {
-        const int form = big ? LOFT_WGRAD_FORM_T256 : LOFT_WGRAD_FORM_T128;
-        if (form_out) { *form_out = form; return 0; }
-        if (form == LOFT_WGRAD_FORM_T256) hipLaunchKernelGGL((conv_wgrad_kernel<256, 8>), grid, dim3(512), 0, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL((conv_wgrad_kernel<128, 4>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    return a;
+}
+
+// The seven forms of this file; the ring and stream forms go to conv_wgrad_pipe.hip.  Neither decides anything: the plan has.
+static int wgrad_launch(const WgradArgs& a, const WgradPlan& p, hipStream_t s) {
+    const dim3 block(p.threads);
+    switch (p.form) {
+    case LOFT_WGRAD_FORM_T256_PM: hipLaunchKernelGGL((conv_wgrad_kernel<256, 8, true>), p.grid, block, 0, s, a); break;
+    case LOFT_WGRAD_FORM_T128_PM: hipLaunchKernelGGL((conv_wgrad_kernel<128, 4, true>), p.grid, block, 0, s, a); break;
+    case LOFT_WGRAD_FORM_NARROW_DENSE: hipLaunchKernelGGL(conv_wgrad64_kernel<1>, p.grid, block, 0, s, a); break;
+    case LOFT_WGRAD_FORM_NARROW_SAME: hipLaunchKernelGGL(conv_wgrad64_kernel<2>, p.grid, block, 0, s, a); break;
+    case LOFT_WGRAD_FORM_NARROW_GENERIC: hipLaunchKernelGGL(conv_wgrad64_kernel<0>, p.grid, block, 0, s, a); break;
+    case LOFT_WGRAD_FORM_T256: hipLaunchKernelGGL((conv_wgrad_kernel<256, 8>), p.grid, block, 0, s, a); break;
+    case LOFT_WGRAD_FORM_T128: hipLaunchKernelGGL((conv_wgrad_kernel<128, 4>), p.grid, block, 0, s, a); break;
+    default: return loft_launch_conv_wgrad_pipe(a, p, s);
     }
     LOFT_LAUNCH_CHECK();
     return 0;
+}
+
+// plan -> build -> launch; nothing to launch (form NONE) is not an error
+static int wgrad_run(const WgradOperands& o, const WgradShape& g, const WgradPlan& p, int partial, void* stream) {
+    if (p.form == LOFT_WGRAD_FORM_NONE) return 0;
+    return wgrad_launch(wgrad_args_build(o, g, p, partial), p, (hipStream_t)stream);
 }
 
 LOFT_EXPORT int loft_conv_wgrad_bf16_v(const void* g, const void* x, float* dw, const void* zero_page, int B, int GH,
@@ -1814,8 +1854,34 @@ LOFT_EXPORT int loft_conv_wgrad_bf16_v(const void* g, const void* x, float* dw, 
                                        const int* goy_host, const int* gox_host, const int* dy_host, const int* dx_host,
                                        const int* wt_host, int groups, int64_t g_gs, int64_t x_gs, int64_t dw_gs,
                                        int splits, float* db, int db_tap, int variant, void* stream) {
-    return wgrad_impl(g, x, dw, zero_page, B, GH, GW, Cout, XH, XW, Cin, OH, OW, gos, ss, T, goy_host, gox_host, dy_host, dx_host,
-                      wt_host, groups, g_gs, x_gs, dw_gs, splits, db, db_tap, variant, stream, 0, nullptr);
+    const WgradShape sh{B, GH, GW, Cout, XH, XW, Cin, OH, OW, gos, ss, T, goy_host, gox_host, dy_host, dx_host, wt_host, groups};
+    WgradPlan p;
+    if (const int e = wgrad_plan(sh, WgradAsk{variant, splits, 0, nullptr, nullptr, false, db != nullptr}, &p)) return e;
+    return wgrad_run(WgradOperands{g, x, dw, zero_page, g_gs, x_gs, dw_gs, db, db_tap, nullptr}, sh, p, 0, stream);
+}
+
+LOFT_EXPORT int loft_conv_wgrad_bf16(const void* g, const void* x, float* dw, const void* zero_page, int B, int GH,
+                                     int GW, int Cout, int XH, int XW, int Cin, int OH, int OW, int gos, int ss, int T,
+                                     const int* goy_host, const int* gox_host, const int* dy_host, const int* dx_host,
+                                     const int* wt_host, int groups, int64_t g_gs, int64_t x_gs, int64_t dw_gs,
+                                     int splits, float* db, int db_tap, void* stream) {
+    return loft_conv_wgrad_bf16_v(g, x, dw, zero_page, B, GH, GW, Cout, XH, XW, Cin, OH, OW, gos, ss, T, goy_host, gox_host, dy_host,
+                                  dx_host, wt_host, groups, g_gs, x_gs, dw_gs, splits, db, db_tap, LOFT_WGRAD_AUTO, stream);
+}
+
+// Split-K slots: every workgroup STORES its tile into its split's slot of dw_slots = [group][nslots][T][Cout][Cin] (see
+// WgradArgs::partial); nslots must be what loft_conv_wgrad_slots answers for these arguments.
+LOFT_EXPORT int loft_conv_wgrad_bf16_slots(const void* g, const void* x, float* dw_slots, const void* zero_page, int B, int GH,
+                                           int GW, int Cout, int XH, int XW, int Cin, int OH, int OW, int gos, int ss, int T,
+                                           const int* goy_host, const int* gox_host, const int* dy_host, const int* dx_host,
+                                           const int* wt_host, int groups, int64_t g_gs, int64_t x_gs, int nslots,
+                                           int splits, float* db, int db_tap, int variant, void* stream) {
+    const WgradShape sh{B, GH, GW, Cout, XH, XW, Cin, OH, OW, gos, ss, T, goy_host, gox_host, dy_host, dx_host, wt_host, groups};
+    WgradPlan p;
+    if (const int e = wgrad_plan(sh, WgradAsk{variant, splits, 0, nullptr, nullptr, true, db != nullptr}, &p)) return e;
+    const int64_t dw_gs = (int64_t)nslots * T * Cout * Cin;
+    if (dw_gs != (int64_t)p.nslots * T * Cout * Cin) return kInvalid;
+    return wgrad_run(WgradOperands{g, x, dw_slots, zero_page, g_gs, x_gs, dw_gs, db, db_tap, nullptr}, sh, p, 1, stream);
 }
 
 // The same contraction on OPERAND PLANES (the fp32 parity mode on the 16-bit matrix cores; see loft_hip.h): g / x hold the planes
@@ -1827,47 +1893,58 @@ LOFT_EXPORT int loft_conv_wgrad_planes(const void* g, const void* x, float* dw, 
                                        const int* wt_host, int groups, int64_t g_gs, int64_t x_gs, int64_t dw_gs,
                                        int nterms, const int* gpl_host, const int* xpl_host, int64_t g_ps, int64_t x_ps,
                                        const float* amax_g, const float* amax_x, float* db, int db_tap, void* stream) {
-    if ((Cin % 128) || (Cout % 128) || (amax_g == nullptr) != (amax_x == nullptr)) return (int)hipErrorInvalidValue;
-    WgradPlanes pl{nterms, gpl_host, xpl_host, g_ps, x_ps, amax_g, amax_x};
-    return wgrad_impl(g, x, dw, zero_page, B, GH, GW, Cout, XH, XW, Cin, OH, OW, gos, ss, T, goy_host, gox_host, dy_host, dx_host,
-                      wt_host, groups, g_gs, x_gs, dw_gs, 0, db, db_tap, LOFT_WGRAD_AUTO, stream, 0, nullptr, &pl);
+    if (nterms < 1 || (amax_g == nullptr) != (amax_x == nullptr)) return kInvalid;
+    const WgradShape sh{B, GH, GW, Cout, XH, XW, Cin, OH, OW, gos, ss, T, goy_host, gox_host, dy_host, dx_host, wt_host, groups};
+    const WgradPlanes pl{nterms, gpl_host, xpl_host, g_ps, x_ps, amax_g, amax_x};
+    WgradPlan p;
+    if (const int e = wgrad_plan(sh, WgradAsk{LOFT_WGRAD_AUTO, 0, nterms, gpl_host, xpl_host, false, db != nullptr}, &p)) return e;
+    return wgrad_run(WgradOperands{g, x, dw, zero_page, g_gs, x_gs, dw_gs, db, db_tap, &pl}, sh, p, 0, stream);
+}
+
+// The host-only queries: wgrad_plan itself, the function the launches call.  include/loft_hip.h has the contracts.
+static int wgrad_query(int B, int GH, int GW, int Cout, int XH, int XW, int Cin, int OH, int OW, int gos, int ss, int T,
+                       const int* goy, const int* gox, const int* dy, const int* dx, const int* wt, int groups, int splits, int variant,
+                       int nterms, WgradPlan* p) {
+    if (nterms < 0 || (nterms && (variant != LOFT_WGRAD_AUTO || splits > 0))) return kInvalid;
+    const WgradShape sh{B, GH, GW, Cout, XH, XW, Cin, OH, OW, gos, ss, T, goy, gox, dy, dx, wt, groups};
+    return wgrad_plan(sh, WgradAsk{variant, splits, nterms, nullptr, nullptr, false, false}, p);
 }
 
 LOFT_EXPORT int loft_conv_wgrad_slots(int B, int GH, int GW, int Cout, int XH, int XW, int Cin, int OH, int OW, int gos, int ss,
                                       int T, const int* goy_host, const int* gox_host, const int* dy_host, const int* dx_host,
                                       const int* wt_host, int groups, int splits, int variant) {
-    int n = 0;
-    const int e = wgrad_impl(nullptr, nullptr, nullptr, nullptr, B, GH, GW, Cout, XH, XW, Cin, OH, OW, gos, ss, T, goy_host,
-                             gox_host, dy_host, dx_host, wt_host, groups, 0, 0, 0, splits, nullptr, -1, variant, nullptr, 1, &n);
-    return e ? -e : n;
+    WgradPlan p;
+    const int e = wgrad_query(B, GH, GW, Cout, XH, XW, Cin, OH, OW, gos, ss, T, goy_host, gox_host, dy_host, dx_host, wt_host, groups,
+                              splits, variant, 0, &p);
+    return e ? -e : (p.slots_ok ? p.nslots : 0);
 }
 
 LOFT_EXPORT int loft_conv_wgrad_form(int B, int GH, int GW, int Cout, int XH, int XW, int Cin, int OH, int OW, int gos, int ss,
                                      int T, const int* goy_host, const int* gox_host, const int* dy_host, const int* dx_host,
                                      const int* wt_host, int groups, int splits, int variant) {
-    int form = LOFT_WGRAD_FORM_NONE;
-    const int e = wgrad_impl(nullptr, nullptr, nullptr, nullptr, B, GH, GW, Cout, XH, XW, Cin, OH, OW, gos, ss, T, goy_host,
-                             gox_host, dy_host, dx_host, wt_host, groups, 0, 0, 0, splits, nullptr, -1, variant, nullptr, 3, &form);
-    return e ? -e : form;
+    WgradPlan p;
+    const int e = wgrad_query(B, GH, GW, Cout, XH, XW, Cin, OH, OW, gos, ss, T, goy_host, gox_host, dy_host, dx_host, wt_host, groups,
+                              splits, variant, 0, &p);
+    return e ? -e : p.form;
 }
 
-LOFT_EXPORT int loft_conv_wgrad_bf16_slots(const void* g, const void* x, float* dw_slots, const void* zero_page, int B, int GH,
-                                           int GW, int Cout, int XH, int XW, int Cin, int OH, int OW, int gos, int ss, int T,
-                                           const int* goy_host, const int* gox_host, const int* dy_host, const int* dx_host,
-                                           const int* wt_host, int groups, int64_t g_gs, int64_t x_gs, int nslots,
-                                           int splits, float* db, int db_tap, int variant, void* stream) {
-    return wgrad_impl(g, x, dw_slots, zero_page, B, GH, GW, Cout, XH, XW, Cin, OH, OW, gos, ss, T, goy_host, gox_host, dy_host,
-                      dx_host, wt_host, groups, g_gs, x_gs, (int64_t)nslots * T * Cout * Cin, splits, db, db_tap, variant, stream, 2,
-                      nullptr);
-}
-
-LOFT_EXPORT int loft_conv_wgrad_bf16(const void* g, const void* x, float* dw, const void* zero_page, int B, int GH,
-                                     int GW, int Cout, int XH, int XW, int Cin, int OH, int OW, int gos, int ss, int T,
-                                     const int* goy_host, const int* gox_host, const int* dy_host, const int* dx_host,
-                                     const int* wt_host, int groups, int64_t g_gs, int64_t x_gs, int64_t dw_gs,
-                                     int splits, float* db, int db_tap, void* stream) {
-    return loft_conv_wgrad_bf16_v(g, x, dw, zero_page, B, GH, GW, Cout, XH, XW, Cin, OH, OW, gos, ss, T, goy_host, gox_host, dy_host,
-                                  dx_host, wt_host, groups, g_gs, x_gs, dw_gs, splits, db, db_tap, LOFT_WGRAD_AUTO, stream);
+LOFT_EXPORT int loft_conv_wgrad_plan(int B, int GH, int GW, int Cout, int XH, int XW, int Cin, int OH, int OW, int gos, int ss,
+                                     int T, const int* goy_host, const int* gox_host, const int* dy_host, const int* dx_host,
+                                     const int* wt_host, int groups, int splits, int variant, int nterms, int* plan_out) {
+    WgradPlan p;
+    if (const int e = wgrad_query(B, GH, GW, Cout, XH, XW, Cin, OH, OW, gos, ss, T, goy_host, gox_host, dy_host, dx_host, wt_host,
+                                  groups, splits, variant, nterms, &p)) return e;
+    static_assert(LOFT_WGRAD_PLAN_PM_PPS == LOFT_WGRAD_PLAN_PM_NS + CONV_MAX_TAPS && LOFT_WGRAD_PLAN_LEN == LOFT_WGRAD_PLAN_PM_PPS + CONV_MAX_TAPS,
+                  "the header's plan_out layout holds one entry per tap of CONV_MAX_TAPS in each table");
+    const int head[LOFT_WGRAD_PLAN_PM_NS] = {p.form, p.tile, p.threads, (int)p.grid.x, (int)p.grid.y, (int)p.grid.z, p.splits,
+                                             p.pix_per_split, p.slots_ok ? p.nslots : 0, p.pm ? 1 : 0};
+    std::copy(head, head + LOFT_WGRAD_PLAN_PM_NS, plan_out);
+    for (int t = 0; t < CONV_MAX_TAPS; ++t) {
+        const bool on = p.pm && t < T;
+        plan_out[LOFT_WGRAD_PLAN_PM_NS + t] = on ? p.pmt.blk0[t + 1] - p.pmt.blk0[t] : 0;
+        plan_out[LOFT_WGRAD_PLAN_PM_PPS + t] = on ? p.pmt.pps[t] : 0;
+    }
+    return 0;
 }
 
 // =====================================================================================

@@ -346,3 +346,58 @@ struct WgradArgs {
 
 __device__ __forceinline__ int wswz(int row, int q) { return q ^ ((row & 3) << 2); }
 
+// ---- host side of a weight-gradient launch (loft_conv_wgrad_*: include/loft_hip.h has the contract): the shape as the C ABI hands
+// it over, what the caller asks for, and the plan -- ALL that conv_mfma.hip decides (wgrad_plan) and all it hands to
+// conv_wgrad_pipe.hip besides the WgradArgs that wgrad_args_build filled.
+struct WgradShape {
+    int B, GH, GW, Cout, XH, XW, Cin, OH, OW, gos, ss, T;
+    const int *goy, *gox, *dy, *dx, *wt;      // HOST tables, T entries each
+    int groups;
+};
+struct WgradAsk {
+    int variant, splits;      // a LOFT_WGRAD_* code; splits <= 0: the library's split-K factor
+    int nterms;               // > 0: an operand-plane launch, `groups * nterms` virtual groups (WgradArgs::nvg)
+    const int *gpl, *xpl;     // HOST term lists of a plane launch (null: a query, which has none to check)
+    bool want_slots, has_db;  // split-K slots written with stores (WgradArgs::partial) / a fused bias gradient
+};
+// The PM fields of WgradArgs (which documents them), under their names there without the prefix; copied over verbatim.
+struct WgradPmTables {
+    int blk0[CONV_MAX_TAPS + 1], pps[CONV_MAX_TAPS], rows[CONV_MAX_TAPS];
+    unsigned pps_mul[CONV_MAX_TAPS], pps_sh[CONV_MAX_TAPS];
+    unsigned char tap[WGRAD_PM_MAX_BLOCKS], split[WGRAD_PM_MAX_BLOCKS];
+    int y0[CONV_MAX_TAPS], x0[CONV_MAX_TAPS], rw[CONV_MAX_TAPS];
+    unsigned rw_mul[CONV_MAX_TAPS], rw_sh[CONV_MAX_TAPS], b_mul, b_sh;
+};
+struct WgradPlan {
+    int form;                 // the LOFT_WGRAD_FORM_* code of the kernel that launches; LOFT_WGRAD_FORM_NONE (0): nothing launches
+    int tile, threads;        // edge of a workgroup's Cout x Cin tile (64 / 128 / 256), threads of a workgroup
+    dim3 grid;                // (channel tiles, taps x groups, K-splits); PM: (channel tiles, groups, blocks of all taps)
+    int ctiles;               // Cin tiles (WgradArgs::ctiles)
+    int vgroups;              // groups of the launch: groups, or groups x terms of a plane launch
+    int splits;               // K-splits of a tap; PM: the split target its block budget min(splits * T, 256) came from
+    int pix_per_split;        // WgradArgs::pix_per_split
+    int nslots;               // WgradArgs::nslots: K-splits of the tap that has the most
+    bool slots_ok;            // a slot launch of this shape exists: wide channels, every weight tap written by exactly one tap, and
+                              // (PM) every tap has a split
+    bool pm;                  // the valid-rows form of RoI maps, with the tables below
+    int pm_inc_ok;            // WgradArgs::pm_inc_ok
+    WgradPmTables pmt;
+};
+// Operand planes of a weight-gradient launch (loft_conv_wgrad_planes): virtual group grp * nterms + p reads G plane gpl[p] / X plane
+// xpl[p] of real group grp and adds into that group's dW.
+struct WgradPlanes {
+    int nterms;
+    const int *gpl, *xpl;
+    long g_ps, x_ps;          // elements between two planes of G / X
+    const float *amax_g, *amax_x;
+};
+struct WgradOperands {
+    const void *g, *x;
+    float* dw;
+    const void* zero_page;
+    long g_gs, x_gs, dw_gs;   // elements between two groups
+    float* db;
+    int db_tap;
+    const WgradPlanes* planes;   // null: a plain launch
+};
+

@@ -379,29 +379,6 @@ __global__ __launch_bounds__(512) void conv_wgrad_stream_kernel(const WgradArgs 
         }
 }
 
-// host side: launched from loft_conv_wgrad_bf16_v (conv_mfma.hip).  Requires Cout % 256 == 0 and Cin % 256 == 0.
-// form_out (loft_conv_wgrad_form): the LOFT_WGRAD_FORM_* code of the kernel chosen below, and nothing is launched.
-int loft_launch_conv_wgrad_stream(const WgradArgs& a, dim3 grid, bool pm, hipStream_t s, int* form_out) {
-    const bool samesize = a.gos == 1 && a.ss == 1 && a.GH == a.OH && a.GW == a.OW && a.XH == a.OH && a.XW == a.OW;
-    bool same = samesize && a.OW >= 64;
-    for (int t = 0; t < a.T; ++t) same = same && a.goy[t] == 0 && a.gox[t] == 0;
-    const bool dense = samesize && a.T == 1 && a.goy[0] == 0 && a.gox[0] == 0 && a.dy[0] == 0 && a.dx[0] == 0;
-    bool inc = pm && a.pm_inc_ok;
-    for (int t = 0; t < a.T && inc; ++t) inc = a.pm_blk0[t + 1] == a.pm_blk0[t] || a.pm_pps[t] >= 64;
-    const int form = (pm && inc) ? LOFT_WGRAD_FORM_STREAM_PM_INC : pm ? LOFT_WGRAD_FORM_STREAM_PM : dense ? LOFT_WGRAD_FORM_STREAM_DENSE
-                     : same ? LOFT_WGRAD_FORM_STREAM_SAME : LOFT_WGRAD_FORM_STREAM_GENERIC;
-    if (form_out) { *form_out = form; return 0; }
-    switch (form) {
-    case LOFT_WGRAD_FORM_STREAM_PM_INC: hipLaunchKernelGGL(conv_wgrad_stream_kernel<1>, grid, dim3(512), 0, s, a); break;
-    case LOFT_WGRAD_FORM_STREAM_PM: hipLaunchKernelGGL(conv_wgrad_stream_kernel<4>, grid, dim3(512), 0, s, a); break;
-    case LOFT_WGRAD_FORM_STREAM_DENSE: hipLaunchKernelGGL(conv_wgrad_stream_kernel<2>, grid, dim3(512), 0, s, a); break;
-    case LOFT_WGRAD_FORM_STREAM_SAME: hipLaunchKernelGGL(conv_wgrad_stream_kernel<3>, grid, dim3(512), 0, s, a); break;
-    default: hipLaunchKernelGGL(conv_wgrad_stream_kernel<0>, grid, dim3(512), 0, s, a); break;
-    }
-    LOFT_LAUNCH_CHECK();
-    return 0;
-}
-
 // =====================================================================================
 // conv_wgrad_ring_kernel -- the 128 x 128 tile (Cout / Cin multiples of 128 but not of 256, or too little K per tile for the
 // 256 form: the backbone's 1x1 and 3x3 layers) with a FOUR-stage ring of 32-pixel K-steps instead of conv_wgrad_kernel<128,4>'s
@@ -621,17 +598,20 @@ __global__ __launch_bounds__(256) void conv_wgrad_ring_kernel(const WgradArgs a)
         }
 }
 
-int loft_launch_conv_wgrad_ring(const WgradArgs& a, dim3 grid, hipStream_t s, int* form_out) {
-    const bool dense = a.T == 1 && a.gos == 1 && a.ss == 1 && a.goy[0] == 0 && a.gox[0] == 0 && a.dy[0] == 0 && a.dx[0] == 0 &&
-                       a.GH == a.OH && a.GW == a.OW && a.XH == a.OH && a.XW == a.OW;
-    bool same = a.gos == 1 && a.ss == 1 && a.GH == a.OH && a.GW == a.OW && a.XH == a.OH && a.XW == a.OW && a.OW >= 32;
-    for (int t = 0; t < a.T; ++t) same = same && a.goy[t] == 0 && a.gox[t] == 0;
-    const int form = dense ? LOFT_WGRAD_FORM_RING_DENSE : same ? LOFT_WGRAD_FORM_RING_SAME : LOFT_WGRAD_FORM_RING_GENERIC;
-    if (form_out) { *form_out = form; return 0; }
-    switch (form) {
-    case LOFT_WGRAD_FORM_RING_DENSE: hipLaunchKernelGGL(conv_wgrad_ring_kernel<1>, grid, dim3(256), 0, s, a); break;
-    case LOFT_WGRAD_FORM_RING_SAME: hipLaunchKernelGGL(conv_wgrad_ring_kernel<2>, grid, dim3(256), 0, s, a); break;
-    default: hipLaunchKernelGGL(conv_wgrad_ring_kernel<0>, grid, dim3(256), 0, s, a); break;
+// host side: the eight forms of this file, launched from wgrad_launch (conv_mfma.hip) with the plan wgrad_plan made there -- form,
+// grid and block threads are the plan's, nothing is decided here.  (Stream forms: Cout, Cin multiples of 256; ring: of 128.)
+int loft_launch_conv_wgrad_pipe(const WgradArgs& a, const WgradPlan& p, hipStream_t s) {
+    const dim3 block(p.threads);
+    switch (p.form) {
+    case LOFT_WGRAD_FORM_STREAM_PM_INC: hipLaunchKernelGGL(conv_wgrad_stream_kernel<1>, p.grid, block, 0, s, a); break;
+    case LOFT_WGRAD_FORM_STREAM_PM: hipLaunchKernelGGL(conv_wgrad_stream_kernel<4>, p.grid, block, 0, s, a); break;
+    case LOFT_WGRAD_FORM_STREAM_DENSE: hipLaunchKernelGGL(conv_wgrad_stream_kernel<2>, p.grid, block, 0, s, a); break;
+    case LOFT_WGRAD_FORM_STREAM_SAME: hipLaunchKernelGGL(conv_wgrad_stream_kernel<3>, p.grid, block, 0, s, a); break;
+    case LOFT_WGRAD_FORM_STREAM_GENERIC: hipLaunchKernelGGL(conv_wgrad_stream_kernel<0>, p.grid, block, 0, s, a); break;
+    case LOFT_WGRAD_FORM_RING_DENSE: hipLaunchKernelGGL(conv_wgrad_ring_kernel<1>, p.grid, block, 0, s, a); break;
+    case LOFT_WGRAD_FORM_RING_SAME: hipLaunchKernelGGL(conv_wgrad_ring_kernel<2>, p.grid, block, 0, s, a); break;
+    case LOFT_WGRAD_FORM_RING_GENERIC: hipLaunchKernelGGL(conv_wgrad_ring_kernel<0>, p.grid, block, 0, s, a); break;
+    default: return (int)hipErrorInvalidValue;      // (not a form of this file: wgrad_launch serves the others)
     }
     LOFT_LAUNCH_CHECK();
     return 0;

@@ -1083,28 +1083,27 @@ def conv_wgrad(g, x, B, GH, GW, Cout, XH, XW, Cin, OH, OW, taps, n_wtaps, gos=1,
                 'loft_conv_wgrad_patch_bf16')
         _prof_end(_ev, 'conv_wgrad', 2.0 * groups * B * OH * OW * Cout * Cin * len(taps), (groups, B, OH, OW, Cin, Cout, len(taps), ss, gos))
         return dw
-    use_slots = WGRAD_SLOTS(groups, B, OH, OW, Cin, Cout, len(taps), ss, gos) if callable(WGRAD_SLOTS) else WGRAD_SLOTS
-    if slots_ok and use_slots and dw is None and n_wtaps == len(taps):
-        S = lib.loft_conv_wgrad_slots(B, GH, GW, Cout, XH, XW, Cin, OH, OW, gos, ss, len(taps), A(0), A(1), A(2), A(3), A(4),
-                                      groups, splits, int(_wgrad_variant(groups, B, OH, OW, Cin, Cout, len(taps), ss, gos)))
+    T = len(taps)
+    shape = (groups, B, OH, OW, Cin, Cout, T, ss, gos)
+    variant = int(_wgrad_variant(*shape))
+    goy, gox, dy, dx, wt = A(0), A(1), A(2), A(3), A(4)
+    S = 0
+    if slots_ok and dw is None and n_wtaps == T and (WGRAD_SLOTS(*shape) if callable(WGRAD_SLOTS) else WGRAD_SLOTS):
+        S = lib.loft_conv_wgrad_slots(B, GH, GW, Cout, XH, XW, Cin, OH, OW, gos, ss, T, goy, gox, dy, dx, wt, groups, splits, variant)
         if S < 0:
             L.check(-S, 'loft_conv_wgrad_slots')
-        if S >= 1:
-            dw = pooled_scratch((groups, S, n_wtaps, Cout, Cin), g.device)
-            L.check(lib.loft_conv_wgrad_bf16_slots(L.ptr(g), L.ptr(x), L.ptr(dw), L.ptr(zero_page(g.device)), B, GH, GW, Cout, XH,
-                                                   XW, Cin, OH, OW, gos, ss, len(taps), A(0), A(1), A(2), A(3), A(4), groups,
-                                                   g_gs, x_gs, S, splits, L.ptr(db), int(db_tap),
-                                                   int(_wgrad_variant(groups, B, OH, OW, Cin, Cout, len(taps), ss, gos)), L.stream()), 'loft_conv_wgrad_bf16_slots')
-            _prof_end(_ev, 'conv_wgrad', 2.0 * groups * B * OH * OW * Cout * Cin * len(taps), (groups, B, OH, OW, Cin, Cout, len(taps), ss, gos))
-            return dw
-    if dw is None:
-        dw = pooled_zeros((groups, n_wtaps, Cout, Cin), g.device)
-    L.check(lib.loft_conv_wgrad_bf16_v(L.ptr(g), L.ptr(x), L.ptr(dw), L.ptr(zero_page(g.device)), B, GH, GW, Cout, XH,
-                                       XW, Cin, OH, OW, gos, ss, len(taps), A(0), A(1), A(2), A(3), A(4), groups,
-                                       g_gs, x_gs, n_wtaps * Cout * Cin, splits, L.ptr(db),
-                                       int(db_tap), int(_wgrad_variant(groups, B, OH, OW, Cin, Cout, len(taps), ss, gos)), L.stream()),
-            'loft_conv_wgrad_bf16_v')
-    _prof_end(_ev, 'conv_wgrad', 2.0 * groups * B * OH * OW * Cout * Cin * len(taps), (groups, B, OH, OW, Cin, Cout, len(taps), ss, gos))
+    if S >= 1:
+        dw = pooled_scratch((groups, S, n_wtaps, Cout, Cin), g.device)
+        L.check(lib.loft_conv_wgrad_bf16_slots(L.ptr(g), L.ptr(x), L.ptr(dw), L.ptr(zero_page(g.device)), B, GH, GW, Cout, XH, XW, Cin,
+                                               OH, OW, gos, ss, T, goy, gox, dy, dx, wt, groups, g_gs, x_gs, S, splits, L.ptr(db),
+                                               int(db_tap), variant, L.stream()), 'loft_conv_wgrad_bf16_slots')
+    else:
+        if dw is None:
+            dw = pooled_zeros((groups, n_wtaps, Cout, Cin), g.device)
+        L.check(lib.loft_conv_wgrad_bf16_v(L.ptr(g), L.ptr(x), L.ptr(dw), L.ptr(zero_page(g.device)), B, GH, GW, Cout, XH, XW, Cin, OH,
+                                           OW, gos, ss, T, goy, gox, dy, dx, wt, groups, g_gs, x_gs, n_wtaps * Cout * Cin, splits,
+                                           L.ptr(db), int(db_tap), variant, L.stream()), 'loft_conv_wgrad_bf16_v')
+    _prof_end(_ev, 'conv_wgrad', 2.0 * groups * B * OH * OW * Cout * Cin * T, shape)
     return dw
 
 
@@ -1128,6 +1127,35 @@ def conv_wgrad_form(B, GH, GW, Cout, XH, XW, Cin, OH, OW, taps, gos=1, ss=1, gro
     if f < 0:
         L.check(-f, 'loft_conv_wgrad_form')
     return f
+
+
+# LOFT_WGRAD_PLAN_*: the indices of loft_conv_wgrad_plan's plan_out (tests/test_lib_symbols.py holds them to include/loft_hip.h)
+(WGRAD_PLAN_FORM, WGRAD_PLAN_TILE, WGRAD_PLAN_THREADS, WGRAD_PLAN_GRID_X, WGRAD_PLAN_GRID_Y, WGRAD_PLAN_GRID_Z, WGRAD_PLAN_SPLITS,
+ WGRAD_PLAN_PIX_PER_SPLIT, WGRAD_PLAN_NSLOTS, WGRAD_PLAN_PM, WGRAD_PLAN_PM_NS) = range(11)
+WGRAD_PLAN_PM_PPS, WGRAD_PLAN_LEN = 26, 42
+WgradPlan = collections.namedtuple('WgradPlan', 'form tile threads grid splits pix_per_split nslots pm pm_splits pm_pps')
+
+
+def conv_wgrad_plan(B, GH, GW, Cout, XH, XW, Cin, OH, OW, taps, gos=1, ss=1, groups=1, splits=0, variant=None, nterms=0):
+    """The plan of the launch conv_wgrad makes for 16-bit operands of this geometry (arguments of conv_wgrad_form; nterms > 0: the
+    operand-plane launch of the fp32 mode with that many terms) -> WgradPlan(form = the WGRAD_FORM_* code; tile edge; threads of a
+    workgroup; grid (x, y, z); K-splits of a tap -- valid-rows form: the split target; rows per split; nslots as
+    loft_conv_wgrad_slots reports it; pm = the valid-rows form of RoI maps, then per tap its K-splits and RoIs per split).  Asks
+    the plan function of the launch path itself (loft_conv_wgrad_plan); touches no device.  Raises LoftHipError where the launch
+    returns hipErrorInvalidValue."""
+    lib = L.load()
+    A = lambda i: L.arr(c_int, [t[i] for t in taps])
+    T = len(taps)
+    if variant is None:
+        variant = _wgrad_variant(groups, B, OH, OW, Cin, Cout, T, ss, gos)
+    o = L.arr(c_int, [0] * WGRAD_PLAN_LEN)
+    L.check(lib.loft_conv_wgrad_plan(B, GH, GW, Cout, XH, XW, Cin, OH, OW, gos, ss, T, A(0), A(1), A(2), A(3), A(4), groups, splits,
+                                     int(variant), nterms, o), 'loft_conv_wgrad_plan')
+    pm = bool(o[WGRAD_PLAN_PM])
+    return WgradPlan(o[WGRAD_PLAN_FORM], o[WGRAD_PLAN_TILE], o[WGRAD_PLAN_THREADS],
+                     (o[WGRAD_PLAN_GRID_X], o[WGRAD_PLAN_GRID_Y], o[WGRAD_PLAN_GRID_Z]), o[WGRAD_PLAN_SPLITS], o[WGRAD_PLAN_PIX_PER_SPLIT],
+                     o[WGRAD_PLAN_NSLOTS], pm,
+                     tuple(o[WGRAD_PLAN_PM_NS:WGRAD_PLAN_PM_NS + T]) if pm else (), tuple(o[WGRAD_PLAN_PM_PPS:WGRAD_PLAN_PM_PPS + T]) if pm else ())
 
 
 def conv2d_wgrad(g, x, R, S, stride=1, pad=0, groups=1, splits=0, with_bias=False, slots_ok=False):

@@ -423,8 +423,9 @@ int loft_conv_wgrad_slots(int B, int GH, int GW, int Cout, int XH, int XW, int C
                           const int* goy_host, const int* gox_host, const int* dy_host, const int* dx_host, const int* wt_host,
                           int groups, int splits, int variant);
 /* Which kernel loft_conv_wgrad_bf16_v (and, the split-K mode aside, loft_conv_wgrad_bf16_slots) launches for these arguments: the
- * launch path itself, stopped before the launch -- no device is touched.  -> a LOFT_WGRAD_FORM_* code (tile family and
- * sub-form), or -hipError_t for arguments the launch rejects.  For tests: a shape written for one form must keep reaching it. */
+ * form of the plan those launches make (wgrad_plan, conv_mfma.hip) -- host arithmetic, no device is touched.  -> a
+ * LOFT_WGRAD_FORM_* code (tile family and sub-form), or -hipError_t for arguments the launch rejects.  loft_conv_wgrad_slots
+ * reads the slot count of the same plan.  For tests: a shape written for one form must keep reaching it. */
 #define LOFT_WGRAD_FORM_NONE 0            /* nothing is launched (no pixel, or no tap of a RoI map has a valid row) */
 #define LOFT_WGRAD_FORM_T128 1            /* conv_wgrad_kernel<128,4> */
 #define LOFT_WGRAD_FORM_T128_PM 2         /* conv_wgrad_kernel<128,4,true>: valid rows only (RoI maps) */
@@ -444,6 +445,28 @@ int loft_conv_wgrad_slots(int B, int GH, int GW, int Cout, int XH, int XW, int C
 int loft_conv_wgrad_form(int B, int GH, int GW, int Cout, int XH, int XW, int Cin, int OH, int OW, int gos, int ss, int T,
                          const int* goy, const int* gox, const int* dy, const int* dx, const int* wt, int groups, int splits,
                          int variant);
+/* The whole plan of such a launch, host only: the arguments of loft_conv_wgrad_form, and nterms > 0 for the launch of
+ * loft_conv_wgrad_planes with that many terms (which has no variant and no splits: pass LOFT_WGRAD_AUTO and 0).  -> 0 and
+ * plan_out[0..LOFT_WGRAD_PLAN_LEN), or hipErrorInvalidValue (1) exactly when the launch returns it for these arguments.  (Not seen
+ * from here, because the query has neither operands nor term lists: the two rules of loft_conv_wgrad_planes about them -- a fused
+ * db needs every G plane paired with X plane 0 in exactly one term, and amax_g / amax_x come both or neither.)  Form
+ * LOFT_WGRAD_FORM_NONE: every other entry is 0.  tests/test_wgrad_plan_cpu.py holds grid, splits and the PM tables to a restatement. */
+#define LOFT_WGRAD_PLAN_FORM 0            /* the LOFT_WGRAD_FORM_* code loft_conv_wgrad_form returns */
+#define LOFT_WGRAD_PLAN_TILE 1            /* edge of a workgroup's Cout x Cin tile: 64 / 128 / 256 */
+#define LOFT_WGRAD_PLAN_THREADS 2         /* threads of a workgroup */
+#define LOFT_WGRAD_PLAN_GRID_X 3          /* channel tiles: ceil(Cout / tile) * ceil(Cin / tile) */
+#define LOFT_WGRAD_PLAN_GRID_Y 4          /* T * groups (* nterms); PM: groups (* nterms) */
+#define LOFT_WGRAD_PLAN_GRID_Z 5          /* K-splits; PM: the blocks of all taps together (<= 256) */
+#define LOFT_WGRAD_PLAN_SPLITS 6          /* K-splits of a tap; PM: the split target, whose block budget is min(splits * T, 256) */
+#define LOFT_WGRAD_PLAN_PIX_PER_SPLIT 7   /* reduction rows of a split, a multiple of 64 (PM: of that target; the launch uses PM_PPS) */
+#define LOFT_WGRAD_PLAN_NSLOTS 8          /* what loft_conv_wgrad_slots returns */
+#define LOFT_WGRAD_PLAN_PM 9              /* 1: the valid-rows form of RoI maps */
+#define LOFT_WGRAD_PLAN_PM_NS 10          /* [16] PM: K-splits of tap t (0 elsewhere) */
+#define LOFT_WGRAD_PLAN_PM_PPS 26         /* [16] PM: RoIs per split of tap t */
+#define LOFT_WGRAD_PLAN_LEN 42
+int loft_conv_wgrad_plan(int B, int GH, int GW, int Cout, int XH, int XW, int Cin, int OH, int OW, int gos, int ss, int T,
+                         const int* goy, const int* gox, const int* dy, const int* dx, const int* wt, int groups, int splits,
+                         int variant, int nterms, int* plan_out);
 int loft_conv_wgrad_bf16_slots(const void* g, const void* x, float* dw_slots, const void* zero_page, int B, int GH, int GW,
                                int Cout, int XH, int XW, int Cin, int OH, int OW, int gos, int ss, int T, const int* goy_host,
                                const int* gox_host, const int* dy_host, const int* dx_host, const int* wt_host, int groups,
